@@ -15,8 +15,14 @@ With N > 1 the headline matrix is cut into N row blocks, one process per GPU, an
 all-gather of the y blocks over xGMI (strong scaling).  Started as plain `python bench.py --gpus N` (no RANK / WORLD_SIZE in
 the environment) the script is its own launcher (bench_core.spawn_ranks, before torch or HIP are touched).
 
+A plain run measures the headline alone: set-up, untimed products (prewarm) and the W warm-up steps, the K timed steps, and a
+line of the contract keys and `config`.  With --full the correctness gates (host product, the reference's committed report),
+the kernel-alone timing, the secondary legs below, the PMC passes and bench_detail.json come too.  --dump-outputs DIR writes
+the y of the last timed step (a fixed seeded sample of its rows) as DIR/y.npy, so that two builds can be compared output for
+output.
+
 This file is the contract: the flags, the order of the legs, their wall-clock budgets, and the ONE compact JSON line rank 0
-prints LAST on stdout (< 8000 characters at every N: the contract keys, `roofline` and `cpu_baseline` as flat scalars).
+prints LAST on stdout (< 8000 characters at every N: the contract keys, and with --full `roofline` and `cpu_baseline` as flat scalars).
 Everything else -- roofline.others, extra, plans, notes -- goes to bench_detail.json beside this script and to stderr.
 bench_core.py holds the timed region and the headline measurement, bench_legs.py the secondary legs.  A leg that fails, or
 that the budget no longer allows, leaves a `<leg>_error` key on the line; a leg that hangs costs that leg: at --hard-deadline a
@@ -34,6 +40,8 @@ from bench_core import HBM_PEAK_GBS, ROOT, log
 
 LINE_LIMIT = 7600       # characters; the driver parsed 18.7 KB and lost 21.9 KB -- stay far below either
 STRING_LIMIT = 110      # characters of any one string value on the compact line
+DUMP_ROWS = 1 << 21     # --dump-outputs: rows of y written (16 MB of values + 16 MB of row indices)
+DUMP_SEED = 2026
 
 
 def parse():
@@ -49,6 +57,12 @@ def parse():
     ap.add_argument("--kernel", default="auto", choices=["auto", "stream", "vector", "stream-carry", "colsweep", "binned"])
     ap.add_argument("--kernel-param", type=int, default=0)
     ap.add_argument("--x", default="ones", choices=["ones", "random"])
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and every secondary measurement (legs, roofline, CPU baseline, PMC passes, bench_detail.json); "
+                         "without it: set-up, warm-up, the timed steps and the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the y of the last step as DIR/y.npy (float64; a fixed seeded sample of at most "
+                         "%d rows, their indices in DIR/y_rows.npy)" % DUMP_ROWS)
     for leg in ("tjds", "random-model", "samples", "config4", "pwt-tiled", "eighth", "c-layer", "cpu-baseline", "live-traffic", "allgather"):
         ap.add_argument("--no-" + leg, action="store_true")
     ap.add_argument("--chunks", type=int, default=0, help="config 4, N > 1: row chunks per rank (0 = chosen from this run's measurements)")
@@ -67,6 +81,9 @@ def parse():
                     help="N > 1: strong = the same matrix cut into N row blocks (default); weak = N times the matrix")
     a = ap.parse_args()
     a.launch_budget = a.launch_budget or a.hard_deadline + 60.0
+    a.full = a.full or a.pmc_child      # (a --pmc child pass reports its roofline to the parent)
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)
     return a
 
 
@@ -95,9 +112,12 @@ PROTECTED = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "
 
 
 def compact_line(state):
-    """The one stdout line: contract keys, `roofline` / `cpu_baseline` / `config` as flat scalars, nothing nested below them."""
+    """The one stdout line: contract keys, `roofline` / `cpu_baseline` / `config` as flat scalars, nothing nested below them.
+    A plain run (no --full) measures nothing but the headline: its line is the contract keys and `config`."""
     line = scalars(state["head"])
     line["config"] = scalars(state["config"])
+    if not state["full"]:
+        return json.dumps(line, allow_nan=False)
     roof = scalars(state["roofline"])
     for leg, err in state["errors"].items():
         roof[leg + "_error"] = str(err)[:STRING_LIMIT]
@@ -137,7 +157,8 @@ class Emitter:
                 return
             self.done = True
             if self.rank == 0 and self.state.get("head"):
-                write_detail(self.state)
+                if self.state["full"]:
+                    write_detail(self.state)
                 self.state["out"].write(compact_line(self.state) + "\n")
                 self.state["out"].flush()
 
@@ -171,6 +192,19 @@ def write_detail(state):
             log(0, "detail.%s.%s: %s" % (k, name, json.dumps(v, default=str)[:1500]))
 
 
+def dump_outputs(y, out_dir):
+    """--dump-outputs: the y a caller of the timed step receives, as DIR/y.npy (float64), and the rows it holds as DIR/y_rows.npy
+    (float64 indices) -- all rows when there are at most DUMP_ROWS, else the same seeded sample of DUMP_ROWS rows every run."""
+    import numpy as np
+
+    n = y.numel()
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy"), y.cpu().numpy()[rows].astype(np.float64))
+    np.save(os.path.join(out_dir, "y_rows.npy"), rows.astype(np.float64))
+    log(0, "wrote y (%d of %d rows) to %s" % (len(rows), n, out_dir))
+
+
 def main():
     args = parse()
     rank, world, local_rank = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
@@ -189,7 +223,7 @@ def main():
     line_out = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
     state = {"t0": time.time(), "errors": {}, "leg_seconds": {}, "extra": {}, "others": {}, "cpu": None, "roofline": {}, "config": {},
-             "detail_path": args.detail, "leg": "start", "out": line_out}
+             "detail_path": args.detail, "leg": "start", "out": line_out, "full": args.full}
     emitter = None if child else Emitter(state, rank, args.hard_deadline)
     left = lambda: args.budget - (time.time() - state["t0"])
     if args.pmc_child:          # inner run of a counter pass: the headline product only
@@ -198,7 +232,7 @@ def main():
 
     # ---- roofline.traffic measured in this run: rocprofv3 --pmc child passes, before this process touches the GPU (N = 1)
     live, live_others = None, {}
-    if rank == 0 and world == 1 and not args.no_live_traffic and "RANK" not in os.environ:
+    if args.full and rank == 0 and world == 1 and not args.no_live_traffic and "RANK" not in os.environ:
         state["leg"], t_leg = "live_traffic", time.time()
         live = legs.live_traffic(args, budget=min(60.0, left()))
         log(rank, "roofline.traffic: %s" % (live[1] if live else "child passes unavailable, using the committed profile"))
@@ -229,9 +263,27 @@ def main():
     # ---- the headline: CSR (or --format tjds) on the workload; K timed steps between barriers, max over ranks
     state["leg"], t_leg = "headline", time.time()
     blk = core.build_block(sm, sharding, args.workload, args, rank, world)
-    res = core.measure_csr(torch, dist, sm, sharding, blk, args, world, local_rank, rank, args.steps, args.warmup, collective=not args.no_allgather)
+    res = core.measure_csr(torch, dist, sm, sharding, blk, args, world, local_rank, rank, args.steps, args.warmup, collective=not args.no_allgather,
+                           full=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res["y_out"], args.dump_outputs)
     short = ("memplus.mtx x%d block-diagonal (substitute for the SURVEY 8(d) random model; that model: roofline.frac_survey_random_model)"
              % (blk["rows_total"] // blk["base"][0]) if args.workload == "memplus_tiled" else blk["name"])
+    state["config"] = {"workload": short + ", %s, x=%s" % (args.format.upper(), args.x), "format": args.format, "kernel": res["kernel"],
+                       "nnz": int(res["nnz_total"]), "rows": blk["rows_total"], "sharding": "row-block x%d" % world,
+                       "exchange": ("%s all-gather of y" % ("RCCL" if backend == "nccl" else backend)) if world > 1 and not args.no_allgather else "none"}
+    state["head"] = {"metric": "fp64 %s SpMV GFLOP/s (2*nnz flop per product; achieved HBM GB/s in roofline)" % args.format.upper(),
+                     "value": round(2.0 * res["nnz_total"] / res["wall_per_step"] * 1e-9, 2), "unit": "GFLOP/s", "n_gpus": world,
+                     "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(res["wall_per_step"] * 1e3, 5),
+                     "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic"}
+    if not args.full:       # a plain run measures the headline and nothing else
+        res["A"].close()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        if rank == 0:
+            emitter.emit()
+        emitter.done = True
+        return
     roof = core.roofline_of(res, short + ", %s, x=%s" % (args.format.upper(), args.x))
     if live:      # (the binned plan's product of several kernels is priced whole; the column sweep's generations per launch)
         per = 1 if " + " in res["kernel"] else res.get("launches", 1)
@@ -246,14 +298,7 @@ def main():
     if res["golden"]:
         extra["full_size_parity"] = res["golden"]
         roof["y_equals_tiled_reference_y"] = True
-    state["config"] = {"workload": short + ", %s, x=%s" % (args.format.upper(), args.x), "format": args.format, "kernel": res["kernel"],
-                       "nnz": int(res["nnz_total"]), "rows": blk["rows_total"], "sharding": "row-block x%d" % world,
-                       "exchange": ("%s all-gather of y" % ("RCCL" if backend == "nccl" else backend)) if world > 1 and not args.no_allgather else "none"}
     state["roofline"] = roof
-    state["head"] = {"metric": "fp64 %s SpMV GFLOP/s (2*nnz flop per product; achieved HBM GB/s in roofline)" % args.format.upper(),
-                     "value": round(2.0 * res["nnz_total"] / res["wall_per_step"] * 1e-9, 2), "unit": "GFLOP/s", "n_gpus": world,
-                     "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(res["wall_per_step"] * 1e3, 5),
-                     "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic"}
     state["leg_seconds"]["headline"] = time.time() - t_leg
 
     def leg(name, estimate, fn, when=True):

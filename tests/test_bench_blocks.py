@@ -190,7 +190,7 @@ def _state(**roofline_more):
     return {"t0": time.time(), "errors": {}, "leg_seconds": {"headline": 12.3, "tjds": 4.0}, "extra": {"dist": {}}, "others": {"tjds": {"frac": 0.6}},
             "cpu": {"value": 0.9, "unit": "GFLOP/s", "cores": 1, "kind": "port", "host_cpu": "AMD EPYC", "sample": "s" * 400},
             "head": {"metric": "fp64 CSR SpMV GFLOP/s", "value": 850.0, "unit": "GFLOP/s", "n_gpus": 8}, "config": {"workload": "w" * 400, "rows": 1},
-            "roofline": roof, "detail_path": "/nonexistent/bench_detail.json", "out": sys.stdout}
+            "roofline": roof, "detail_path": "/nonexistent/bench_detail.json", "out": sys.stdout, "full": True}
 
 
 def test_compact_line_is_short_flat_and_keeps_the_contract():
@@ -219,6 +219,47 @@ def test_compact_line_is_short_flat_and_keeps_the_contract():
     assert len(text) <= bench.LINE_LIMIT < 8000 and j["roofline"]["dropped_for_length"] is True
     assert all(j["roofline"][k] == v for k, v in flat.items()) and j["roofline"]["ms_per_launch"] == 0.28319
     assert j["roofline"]["config4_c_layer_error"].startswith("timeout") and len(j["roofline"]["config4_c_layer_error"]) <= bench.STRING_LIMIT
+
+
+def test_plain_run_line_is_the_headline_alone():
+    """Without --full the line is the contract keys and `config`: no roofline, no cpu_baseline, no detail file named."""
+    import json
+
+    st = _state()
+    st["full"] = False
+    j = json.loads(bench.compact_line(st))
+    assert j["value"] == 850.0 and j["unit"] == "GFLOP/s" and j["config"]["rows"] == 1
+    assert not {"roofline", "cpu_baseline", "detail"} & set(j)
+
+
+def test_full_is_off_by_default(monkeypatch, tmp_path):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path / "out")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--pmc-child"])        # a --pmc child pass reports the roofline to its parent
+    assert bench.parse().full is True
+
+
+def test_dump_outputs_writes_a_fixed_sample(monkeypatch, tmp_path):
+    """--dump-outputs: y as float64, every row of a small y, and of a large one the same seeded, sorted sample every time."""
+    import torch
+
+    y = torch.arange(1000, dtype=torch.float64) * 0.5
+    bench.dump_outputs(y, str(tmp_path / "all"))
+    assert np.array_equal(np.load(tmp_path / "all" / "y.npy"), y.numpy()) and np.load(tmp_path / "all" / "y.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "all" / "y_rows.npy"), np.arange(1000))
+    assert bench.DUMP_ROWS * 16 < 64 << 20        # y and its row indices, 8 bytes each: within the 64 MB an output dump may take
+    monkeypatch.setattr(bench, "DUMP_ROWS", 64)
+    for d in ("a", "b"):
+        bench.dump_outputs(y, str(tmp_path / d))
+    rows = np.load(tmp_path / "a" / "y_rows.npy")
+    assert len(rows) == 64 and np.all(np.diff(rows) > 0) and rows.max() < 1000
+    assert np.array_equal(np.load(tmp_path / "a" / "y.npy"), rows * 0.5)
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in ("y.npy", "y_rows.npy"))
 
 
 def test_watchdog_prints_the_line_when_a_leg_hangs(tmp_path):

@@ -1258,14 +1258,14 @@ def test_uniform32_config4_shape(torch):
 
 
 def _bench(tmp_path, argv, env=None, timeout=900):
-    """bench.py as the driver runs it -> (the parsed LAST stdout line, its text, bench_detail.json)."""
+    """bench.py --full as the driver runs it -> (the parsed LAST stdout line, its text, bench_detail.json)."""
     import json
     import sys
 
     from conftest import ROOT
 
     detail = str(tmp_path / "bench_detail.json")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + ["--detail", detail], capture_output=True, text=True, env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + argv + ["--detail", detail], capture_output=True, text=True, env=env,
                        timeout=timeout)
     assert p.returncode == 0, p.stderr[-3000:]
     out = p.stdout.splitlines()
@@ -1339,7 +1339,7 @@ def test_bench_budget_skips_legs_and_keeps_the_line(torch, tmp_path):
     from conftest import ROOT
 
     detail = str(tmp_path / "d.json")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--copies", "8", "--rows", "300000", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--copies", "8", "--rows", "300000", "--steps", "3", "--warmup", "1",
                         "--no-live-traffic", "--budget", "1", "--detail", detail], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     j = json.loads(p.stdout.splitlines()[-1])
@@ -1348,6 +1348,36 @@ def test_bench_budget_skips_legs_and_keeps_the_line(torch, tmp_path):
     for leg in ("tjds", "cpu_baseline", "config4", "survey_random_model", "pwt_tiled"):
         assert r[leg + "_error"].startswith("skipped"), leg
     assert "frac_config4" not in r and len(p.stdout.splitlines()[-1]) < 8000
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_y(torch, tmp_path):
+    """A plain run (no --full): ONE line of the contract keys and `config`, no secondary leg, no correctness pass, no detail file;
+    --dump-outputs writes the last timed step's y -- tile(memplus row sums) at x = ones -- the same rows run after run."""
+    import json
+    import sys
+
+    from conftest import ROOT
+
+    m, n, coo = load("memplus.mtx")
+    rp, ci, v = sm.csr_from_coo(coo, m)
+    want, scale = np.tile(np.add.reduceat(v, rp[:-1]), 8), np.tile(np.add.reduceat(np.abs(v), rp[:-1]), 8)
+    ys = []
+    for run in ("a", "b"):
+        detail, out = tmp_path / ("detail_%s.json" % run), tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--copies", "8", "--steps", "4", "--warmup", "1", "--dump-outputs",
+                            str(out), "--detail", str(detail)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = p.stdout.splitlines()
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["steps"] == 4 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0 and j["higher_is_better"] is True
+        assert j["unit"] == "GFLOP/s" and j["dtype"] == "f64" and j["metric"].startswith("fp64 CSR SpMV GFLOP/s") and j["config"]["rows"] == 8 * m
+        assert not {"roofline", "cpu_baseline"} & set(j) and not detail.exists() and "correct:" not in p.stderr
+        y, rows = np.load(out / "y.npy"), np.load(out / "y_rows.npy")
+        assert y.dtype == np.float64 and np.array_equal(rows, np.arange(8 * m))
+        assert np.all(np.abs(y - want) <= TOL * scale)
+        ys.append(y)
+    assert np.all(np.abs(ys[0] - ys[1]) <= TOL * scale)
 
 
 def test_bench_starts_its_own_ranks(torch, tmp_path):

@@ -53,9 +53,9 @@ run() {    # $1 = tag, rest = command
 }
 cd $R
 export SMVP_DIST_BACKEND=gloo
-run gloo6 timeout -k 10 900 python3 bench.py --gpus 6 --steps 20 --warmup 5 --rows 1200000 --copies 96
-run gloo2_full timeout -k 10 900 python3 bench.py --gpus 2 --steps 20 --warmup 5
-run gloo4_deadline timeout -k 10 300 python3 bench.py --gpus 4 --steps 20 --warmup 5 --rows 2000000 --copies 96 --hard-deadline 40
+run gloo6 timeout -k 10 900 python3 bench.py --full --gpus 6 --steps 20 --warmup 5 --rows 1200000 --copies 96
+run gloo2_full timeout -k 10 900 python3 bench.py --full --gpus 2 --steps 20 --warmup 5
+run gloo4_deadline timeout -k 10 300 python3 bench.py --full --gpus 4 --steps 20 --warmup 5 --rows 2000000 --copies 96 --hard-deadline 40
 unset SMVP_DIST_BACKEND
-SMVP_FORCE_DIST=1 run rccl1 timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 10 --warmup 2 --no-random-model --no-samples --no-cpu-baseline --no-tjds --no-pwt-tiled --chunks 4
+SMVP_FORCE_DIST=1 run rccl1 timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 1 --steps 10 --warmup 2 --no-random-model --no-samples --no-cpu-baseline --no-tjds --no-pwt-tiled --chunks 4
 cut -c1-400 "$F"

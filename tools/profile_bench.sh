@@ -9,7 +9,7 @@ TAG=${1:-r01}
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/profile_$TAG
 mkdir -p "$OUT"
-ARGS="--no-live-traffic --no-c-layer --no-random-model --no-tjds --no-cpu-baseline --no-samples --no-config4 --no-pwt-tiled ${BENCH_ARGS:-}"
+ARGS="--full --no-live-traffic --no-c-layer --no-random-model --no-tjds --no-cpu-baseline --no-samples --no-config4 --no-pwt-tiled ${BENCH_ARGS:-}"
 PAT=${PAT:-csr_stream_owner<8, 5}   # kernel-name substring the PMC summary is taken over; several, separated by '|', for a product of
                                     # several kernels (the binned plan): their per-launch means are added
 # ONE process gives both the kernel trace and the bench line (bench.json = the stdout of the traced run): the profile's average

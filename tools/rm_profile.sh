@@ -7,7 +7,7 @@ TAG=${1:-x}; shift || true
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r04
 mkdir -p "$OUT"
-ARGS="--workload memplus_shaped --no-tjds --no-samples --no-config4 --no-pwt-tiled --no-cpu-baseline --no-c-layer --no-live-traffic --steps 50 --warmup 5 $*"
+ARGS="--full --workload memplus_shaped --no-tjds --no-samples --no-config4 --no-pwt-tiled --no-cpu-baseline --no-c-layer --no-live-traffic --steps 50 --warmup 5 $*"
 cd /tmp; export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rm_trace_$TAG" -o t -- python3 $R/bench.py $ARGS > "$OUT/rm_$TAG.json" 2> "$OUT/rm_$TAG.log" || { echo "bench failed (a debug build gives wrong results: expected then)"; tail -3 "$OUT/rm_$TAG.log"; }
 cp "$OUT/rm_trace_$TAG/t_kernel_stats.csv" "$OUT/rm_$TAG.kernel_stats.csv"
