@@ -3,9 +3,11 @@
 Tolerances (BASELINE.json north_star):
   - integer arrays (row_ptr/col_ind, perm/start_pos/row_ind): bit-exact -- checked on the host
     in test_host_library.py; here the same arrays feed the kernels.
-  - fp64 y: |y_gpu[r] - y_ref[r]| <= 1e-9 * sum_j |a_rj x_j| for every row (row-normwise relative;
-    memplus has ~200 rows whose true sum cancels to ~1e-15 of their terms, so an element-wise
-    relative bound cannot hold for ANY summation order other than the serial one).
+  - fp64 y (parity.check_y): |y_gpu[r] - y_ref[r]| <= min(1e-9, 2 (n_r + 2) 2^-53) * sum_j |a_rj x_j| for every row of
+    n_r products (row-normwise relative: what two correctly rounded sums of the same products in any order can differ
+    by; memplus has ~200 rows whose true sum cancels to ~1e-15 of their terms, so an element-wise relative bound cannot
+    hold for ANY summation order other than the serial one); a NaN left in a row fails; empty rows are exact.
+  - y lies in a guarded buffer (parity.guarded_y) where the tests allocate it themselves: nothing may be written next to it.
   - pattern matrices (ibm32, curtis54, pwt) and pdp08-pg4 have small-integer sums: exact.
   - rows the stream kernel sums with one lane are bit-identical to the serial oracle.
 """
@@ -20,10 +22,10 @@ import pytest
 import oracle_binding as ob
 import smvp_toolkit_amd as sm
 from conftest import REPORTS, SAMPLES
+from parity import SPILL_KINDS, TOL, assert_spill_regime, check_guards, check_y, guarded_y, spill_matrix
 from test_oracle_golden import _mask
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-9
 EXACT = {"ibm32.mtx", "curtis54.mtx", "pwt.mtx", "pdp08-pg4.mtx"}
 
 CSR_VARIANTS = [(sm.CSR_KERNEL_STREAM, 256), (sm.CSR_KERNEL_STREAM, 1024), (sm.CSR_KERNEL_STREAM, 2048),
@@ -49,26 +51,28 @@ def row_scale(row_ptr, col_ind, val, x):
     return ob.csr_spmv(row_ptr, col_ind, np.abs(val), np.abs(x))
 
 
-def assert_close(y, ref, scale, exact=False):
-    assert y.shape == ref.shape
-    if exact:
-        assert np.array_equal(y, ref)
-    else:
-        bad = np.abs(y - ref) > TOL * scale
-        assert not bad.any(), "%d rows beyond %g * sum|a x|; worst %g" % (
-            bad.sum(), TOL, (np.abs(y - ref) / np.maximum(scale, 1e-300)).max())
+def refquirks_yardsticks(coo, m, n, x):
+    """(scale, terms) of the --ref-quirks product, which sums only some of A's entries: the quirky oracle on |A| and |x|,
+    and on A's pattern with x = ones."""
+    t = ob.tjds_build(coo, m, n)
+    t.val = np.abs(t.val)
+    scale = ob.tjds_spmv(t, np.abs(x), refquirks=True)
+    t.val = np.ones_like(t.val)
+    return scale, ob.tjds_spmv(t, np.ones(n), refquirks=True)
 
 
 def gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, kernel, param):
+    """y = A x through one handle, into a guarded y (parity.guarded_y): NaN in every row before, the guards intact after."""
     A = sm.CsrMatrix(rows, cols, row_ptr, col_ind, val)
     A.set_kernel(kernel, param)
     assert A.get_kernel()[0] == kernel and (param == 0 or A.get_kernel()[1] == param)
     dx = dev(torch, x)
-    dy = torch.full((max(rows, 1),), float("nan"), dtype=torch.float64, device="cuda")
+    buf, dy = guarded_y(torch, rows)
     A.spmv(dx, dy)
     torch.cuda.synchronize()
     A.close()
-    return dy.cpu().numpy()[:rows]
+    check_guards(buf, rows)
+    return dy.cpu().numpy()
 
 
 def load(name):
@@ -85,7 +89,7 @@ def test_csr_sample_matrices_ones(torch, name, kernel, param):
     x = np.ones(n)
     ref = ob.csr_spmv(row_ptr, col_ind, val, x)
     y = gpu_csr(torch, m, n, row_ptr, col_ind, val, x, kernel, param)
-    assert_close(y, ref, row_scale(row_ptr, col_ind, val, x), exact=name in EXACT)
+    check_y(y, ref, row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr), exact=name in EXACT)
     if name in EXACT or kernel in (sm.CSR_KERNEL_STREAM, sm.CSR_KERNEL_STREAM_CARRY):
         # the %g text of the report must equal the reference's committed report
         want = ob.report_y_lines(ob.read_report("smvp-toolbox_report_CSR_%s.txt" % REPORTS[name][0]))
@@ -114,7 +118,7 @@ def test_csr_sample_matrices_general_x(torch, name, kernel, param):
     x = np.random.default_rng(67890).random(n)
     ref = ob.csr_spmv(row_ptr, col_ind, val, x)
     y = gpu_csr(torch, m, n, row_ptr, col_ind, val, x, kernel, param)
-    assert_close(y, ref, row_scale(row_ptr, col_ind, val, x), exact=kernel == sm.CSR_KERNEL_COLSWEEP)   # sweep: serial order
+    check_y(y, ref, row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr), exact=kernel == sm.CSR_KERNEL_COLSWEEP)   # sweep: serial order
 
 
 def test_stream_kernel_is_bitwise_serial_on_short_rows(torch):
@@ -216,7 +220,7 @@ def test_csr_16_bit_column_offsets(torch):
                 A.spmv(dev(torch, x2), dy)
                 torch.cuda.synchronize()
                 got["csr", tile, env] = dy.cpu().numpy()
-                assert_close(got["csr", tile, env], ref2, sc2)
+                check_y(got["csr", tile, env], ref2, sc2, np.diff(rp2))
                 A.close()
                 T = sm.TjdsMatrix(sm.tjds_from_coo(coo2, len(lens), 5000))
                 T.set_tile(tile)
@@ -225,7 +229,7 @@ def test_csr_16_bit_column_offsets(torch):
                 T.spmv(dy)
                 torch.cuda.synchronize()
                 got["tjds", tile, env] = dy.cpu().numpy()
-                assert_close(got["tjds", tile, env], ref2, sc2)
+                check_y(got["tjds", tile, env], ref2, sc2, np.diff(rp2))
                 T.close()
     for fmt in ("csr", "tjds"):
         for tile in (1024, 2048):
@@ -333,7 +337,7 @@ def test_colsweep_rows_that_meet_in_a_chunk(torch):
     scale = row_scale(row_ptr, col_ind, val, x)
     for rb, parts in ((1024, 2), (1024, 4), (5120, 4), (1024, 8), (256, 8)):
         y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_COLSWEEP, sm.sweep_parts(rb, parts))
-        assert_close(y, ref, scale)
+        check_y(y, ref, scale, np.diff(row_ptr))
         assert np.array_equal(y, gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_COLSWEEP, sm.sweep_parts(rb, parts)))
 
 
@@ -363,7 +367,7 @@ def test_binned_plan_on_a_row_block_of_a_sharded_matrix(torch):
         dy = torch.full((n_loc,), float("nan"), dtype=torch.float64, device="cuda")
         M.spmv(dx, dy)
         torch.cuda.synchronize()
-        assert_close(dy.cpu().numpy(), ref, scale)
+        check_y(dy.cpu().numpy(), ref, scale, np.diff(row_ptr))
     # the split is the whole matrix's: 20 B per far entry + 10 B per near slot -- the all-far plan is much larger
     assert A.plan_info()["plan_bytes"] < 0.8 * B.plan_info()["plan_bytes"]
     # the tile kernel's near engine and another band on the offset handle
@@ -371,7 +375,7 @@ def test_binned_plan_on_a_row_block_of_a_sharded_matrix(torch):
     dy = torch.full((n_loc,), float("nan"), dtype=torch.float64, device="cuda")
     A.spmv(dx, dy)
     torch.cuda.synchronize()
-    assert_close(dy.cpu().numpy(), ref, scale)
+    check_y(dy.cpu().numpy(), ref, scale, np.diff(row_ptr))
     A.close()
     B.close()
     # the sharded layer passes every chunk's first row on: 2 and 3 virtual ranks x 2 chunks on the whole model, binned by choice
@@ -384,7 +388,7 @@ def test_binned_plan_on_a_row_block_of_a_sharded_matrix(torch):
         S.set_x(x)
         S.spmv(allgather=sm.GATHER_OVERLAPPED)
         S.synchronize()
-        assert_close(S.get_y(ranks - 1, gathered=True), ref_full, scale_full)
+        check_y(S.get_y(ranks - 1, gathered=True), ref_full, scale_full, np.diff(full[0]))
         S.close()
 
 
@@ -413,7 +417,7 @@ def test_binned_plan_on_the_random_model(torch, near):
         A.spmv(dx, dy)
         torch.cuda.synchronize()
         ys.append(dy.cpu().numpy())
-    assert_close(ys[0], ref, scale)
+    check_y(ys[0], ref, scale, np.diff(row_ptr))
     assert np.array_equal(ys[0], ys[1]) and np.array_equal(ys[0], ys[2])
     rows_of = np.repeat(np.arange(rows), np.diff(row_ptr))
     far = np.abs(col_ind.astype(np.int64) - rows_of) > 4096
@@ -433,7 +437,7 @@ def test_binned_plan_on_the_random_model(torch, near):
     dy = torch.full((rows,), float("nan"), dtype=torch.float64, device="cuda")
     A.spmv(dx, dy)
     torch.cuda.synchronize()
-    assert_close(dy.cpu().numpy(), ref, scale)
+    check_y(dy.cpu().numpy(), ref, scale, np.diff(row_ptr))
     assert A.plan_info()["plan_bytes"] < 3.0 * n
     # other bands, ones as the operand (the reference's), and back to AUTO
     for band in (64, 1 << 20):
@@ -442,14 +446,14 @@ def test_binned_plan_on_the_random_model(torch, near):
         dy.fill_(float("nan"))
         A.spmv(dx, dy)
         torch.cuda.synchronize()
-        assert_close(dy.cpu().numpy(), ref, scale)
+        check_y(dy.cpu().numpy(), ref, scale, np.diff(row_ptr))
     A.set_kernel(sm.CSR_KERNEL_AUTO, 0)
     assert A.get_kernel() == (sm.CSR_KERNEL_BINNED, 4096)
     ones = np.ones(rows)
     dy.fill_(float("nan"))
     A.spmv(dev(torch, ones), dy)
     torch.cuda.synchronize()
-    assert_close(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, ones), row_scale(row_ptr, col_ind, val, ones))
+    check_y(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, ones), row_scale(row_ptr, col_ind, val, ones), np.diff(row_ptr))
     A.close()
 
 
@@ -472,7 +476,7 @@ def test_binned_plan_corner_structures(torch):
     scale = row_scale(row_ptr, col_ind, val, x)
     for band in (0, 5, 2_000_000):
         y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_BINNED, band)
-        assert_close(y, ref, scale)
+        check_y(y, ref, scale, np.diff(row_ptr))
     # tall and narrow: every column within a few blocks, many far rows per row block, rows == 0 far entries in stretches
     rows, cols = 200_000, 40_000
     lens = rng.integers(0, 9, rows)
@@ -480,7 +484,39 @@ def test_binned_plan_corner_structures(torch):
     row_ptr, col_ind, val = csr_from_lengths(rng, lens.tolist(), cols)
     x = rng.random(cols)
     y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_BINNED, 16)
-    assert_close(y, ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x))
+    check_y(y, ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
+
+
+@pytest.mark.parametrize("kind", SPILL_KINDS)
+def test_binned_spill_paths(torch, kind):
+    """The binned plan past its caps (parity.spill_matrix): a column block with more cells than pass A stages shifts for in
+    LDS ("cells"), a row block with more sub-runs than pass B stages ("runs"), row blocks whose far rows span too many rows
+    for the packed far-row list ("fr32": pass B reads fr_row / fr_ptr).  The matrix must reach its regime with 10 % to spare
+    (checked from its own arrays); then, on both near engines, y is the oracle's within the rounding bound, the same bits
+    twice, and nothing is written next to it."""
+    rows, cols, band, row_ptr, col_ind, val = spill_matrix(kind)
+    assert_spill_regime(kind, rows, cols, band, row_ptr, col_ind)
+    x = np.random.default_rng(404).standard_normal(cols)
+    ref = ob.csr_spmv(row_ptr, col_ind, val, x)
+    scale = row_scale(row_ptr, col_ind, val, x)
+    dx = dev(torch, x)
+    for near in (0, 1):
+        sm.set_option("binned_near", near)
+        A = sm.CsrMatrix(rows, cols, row_ptr, col_ind, val)
+        A.set_kernel(sm.CSR_KERNEL_BINNED, band)
+        name = A.describe()[0]
+        assert "csr_binned_far_products" in name and "csr_binned_far_sums" in name, name
+        assert ("csr_near_window" in name) == (near == 0) or kind != "fr32", name
+        ys = []
+        for _ in range(2):
+            buf, dy = guarded_y(torch, rows)
+            A.spmv(dx, dy)
+            torch.cuda.synchronize()
+            check_guards(buf, rows)
+            ys.append(dy.cpu().numpy())
+        A.close()
+        check_y(ys[0], ref, scale, np.diff(row_ptr))
+        assert np.array_equal(ys[0], ys[1]), "%d rows differ from run to run" % (ys[0] != ys[1]).sum()
 
 
 def test_binned_near_engines(torch):
@@ -538,7 +574,7 @@ def test_binned_near_engines(torch):
                 A.spmv(dx, dy)
                 torch.cuda.synchronize()
                 y = dy.cpu().numpy()
-                assert_close(y, ref, scale)
+                check_y(y, ref, scale, np.diff(row_ptr))
                 assert np.array_equal(y, got.setdefault(near, y))            # the same bits, aligned or not, run to run
             A.close()
         short = (np.diff(row_ptr) <= 16)
@@ -556,7 +592,7 @@ def test_binned_near_engines(torch):
     dy = torch.full((rows,), float("nan"), dtype=torch.float64, device="cuda")
     A.spmv(dev(torch, x), dy)
     torch.cuda.synchronize()
-    assert_close(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x))
+    check_y(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
     A.close()
 
 
@@ -657,10 +693,11 @@ def test_auto_plan_choice(torch):
         A = sm.CsrMatrix(len(lens), 50000, row_ptr, col_ind, val)
         assert A.get_kernel()[0] == want
         x = rng.random(50000)
-        dy = torch.empty(len(lens), dtype=torch.float64, device="cuda")
+        buf, dy = guarded_y(torch, len(lens))
         A.spmv(dev(torch, x), dy)
         torch.cuda.synchronize()
-        assert_close(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x))
+        check_guards(buf, len(lens))
+        check_y(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
         A.close()
 
 
@@ -735,7 +772,7 @@ def test_tjds_half_words_with_a_run_per_entry(torch):
             T.set_x(dev(torch, x))
             T.spmv(dy)
             torch.cuda.synchronize()
-            assert_close(dy.cpu().numpy(), ref, row_scale(row_ptr, col_ind, val, x))
+            check_y(dy.cpu().numpy(), ref, row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
     T.close()
 
 
@@ -768,7 +805,7 @@ def test_tjds_half_words_across_position_blocks(torch):
                 torch.cuda.synchronize()
                 if want is None:
                     want = dy.clone()
-                    assert_close(dy.cpu().numpy(), ref, scale)
+                    check_y(dy.cpu().numpy(), ref, scale, np.diff(row_ptr))
                 assert torch.equal(dy, want), (index, tile, cache)
             T.close()
 
@@ -786,14 +823,15 @@ def test_tjds_sample_matrices(torch, name, mode):
     assert ("scatter" in T.describe()[0]) == (mode == sm.TJDS_MODE_ATOMIC)
     for x in (np.ones(n), np.random.default_rng(67890).random(n)):
         ref = ob.csr_spmv(row_ptr, col_ind, val, x)          # a correct TJDS computes A x
-        dy = torch.full((m,), float("nan"), dtype=torch.float64, device="cuda")
+        buf, dy = guarded_y(torch, m)
         T.set_x(dev(torch, x))
         T.zero_y(dy)
         T.spmv(dy)
         torch.cuda.synchronize()
+        check_guards(buf, m)
         y = dy.cpu().numpy()
-        assert_close(y, ref, row_scale(row_ptr, col_ind, val, x), exact=(name in EXACT and x[0] == 1.0))
-        assert_close(y, ob.tjds_spmv(ob.tjds_build(coo, m, n), x), row_scale(row_ptr, col_ind, val, x))
+        check_y(y, ref, row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr), exact=(name in EXACT and x[0] == 1.0))
+        check_y(y, ob.tjds_spmv(ob.tjds_build(coo, m, n), x), row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
     T.close()
 
 
@@ -804,11 +842,12 @@ def test_tjds_ref_quirks_reproduce_committed_reports(torch, name):
     t = sm.tjds_from_coo(coo, m, n)
     T = sm.TjdsMatrix(t)
     T.set_ref_quirks(True)
-    dy = torch.zeros(m, dtype=torch.float64, device="cuda")
+    buf, dy = guarded_y(torch, m)
     T.set_x(dev(torch, np.ones(n)))
     T.zero_y(dy)
     T.spmv(dy)
     torch.cuda.synchronize()
+    check_guards(buf, m)
     y = dy.cpu().numpy()
     want = ob.report_y_lines(ob.read_report("smvp-toolbox_report_TJDS_%s.txt" % REPORTS[name][1]))
     oracle_y = ob.tjds_spmv(ob.tjds_build(coo, m, n), np.ones(n), refquirks=True)
@@ -817,21 +856,22 @@ def test_tjds_ref_quirks_reproduce_committed_reports(torch, name):
         assert np.array_equal(y, oracle_y)
     else:
         # memplus: atomics reorder the sums; compare normwise and the %g text on well-conditioned rows
-        row_ptr, col_ind, val = sm.csr_from_coo(coo, m)
-        scale = row_scale(row_ptr, col_ind, val, np.ones(n))
-        assert_close(y, oracle_y, scale)
+        scale, terms = refquirks_yardsticks(coo, m, n, np.ones(n))
+        check_y(y, oracle_y, scale, terms)
         got = ob.fmt_g(y)
         well = np.abs(oracle_y) > 1e-6 * scale
         diff = [i for i in np.flatnonzero(well) if got[i] != want[i]]
         assert len(diff) <= 0.001 * m
     # back to the corrected product
     T.set_ref_quirks(False)
+    dy.fill_(float("nan"))
     T.zero_y(dy)
     T.spmv(dy)
     torch.cuda.synchronize()
+    check_guards(buf, m)
     row_ptr, col_ind, val = sm.csr_from_coo(coo, m)
-    assert_close(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, np.ones(n)),
-                 row_scale(row_ptr, col_ind, val, np.ones(n)))
+    check_y(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, np.ones(n)),
+            row_scale(row_ptr, col_ind, val, np.ones(n)), np.diff(row_ptr))
     T.close()
 
 
@@ -873,7 +913,7 @@ def test_csr_edge_cases(torch, case, kernel, param):
     x = rng.random(cols)
     ref = ob.csr_spmv(row_ptr, col_ind, val, x)
     y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, kernel, param)
-    assert_close(y, ref, row_scale(row_ptr, col_ind, val, x), exact=kernel == sm.CSR_KERNEL_COLSWEEP)
+    check_y(y, ref, row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr), exact=kernel == sm.CSR_KERNEL_COLSWEEP)
 
 
 @pytest.mark.parametrize("name", SAMPLES)
@@ -884,14 +924,15 @@ def test_tjds_row_gather_variants_on_samples(torch, name, index, tile):
     row_ptr, col_ind, val = sm.csr_from_coo(coo, m)
     T = tjds_gather_matrix(sm.tjds_from_coo(coo, m, n), index, tile)
     for x in (np.ones(n), np.random.default_rng(67890).random(n)):
-        dy = torch.full((m,), float("nan"), dtype=torch.float64, device="cuda")
+        buf, dy = guarded_y(torch, m)
         T.set_x(dev(torch, x))
         T.spmv(dy)
         torch.cuda.synchronize()
+        check_guards(buf, m)
         y = dy.cpu().numpy()
         scale = row_scale(row_ptr, col_ind, val, x)
-        assert_close(y, ob.csr_spmv(row_ptr, col_ind, val, x), scale, exact=(name in EXACT and x[0] == 1.0))
-        assert_close(y, ob.tjds_spmv(ob.tjds_build(coo, m, n), x), scale)
+        check_y(y, ob.csr_spmv(row_ptr, col_ind, val, x), scale, np.diff(row_ptr), exact=(name in EXACT and x[0] == 1.0))
+        check_y(y, ob.tjds_spmv(ob.tjds_build(coo, m, n), x), scale, np.diff(row_ptr))
     T.close()
 
 
@@ -939,10 +980,11 @@ def test_tjds_row_gather_edge_cases(torch, case, index, tile):
     x = rng.random(cols)
     T = tjds_gather_matrix(sm.tjds_from_coo(coo, rows, cols), index, tile)
     T.set_x(dev(torch, x))
-    dy = torch.full((max(rows, 1),), float("nan"), dtype=torch.float64, device="cuda")
+    buf, dy = guarded_y(torch, rows)
     T.spmv(dy)
     torch.cuda.synchronize()
-    assert_close(dy.cpu().numpy()[:rows], ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x))
+    check_guards(buf, rows)
+    check_y(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
     T.close()
 
 
@@ -958,11 +1000,12 @@ def test_tjds_edge_cases_handles(torch, case, mode):
     T = sm.TjdsMatrix(sm.tjds_from_coo(coo, rows, cols))
     T.set_mode(mode)
     T.set_x(dev(torch, x))
-    dy = torch.full((max(rows, 1),), float("nan"), dtype=torch.float64, device="cuda")
+    buf, dy = guarded_y(torch, rows)
     T.zero_y(dy)
     T.spmv(dy)
     torch.cuda.synchronize()
-    assert_close(dy.cpu().numpy()[:rows], ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x))
+    check_guards(buf, rows)
+    check_y(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
 
 
 @pytest.mark.parametrize("case", sorted(EDGE_CASES))
@@ -976,9 +1019,9 @@ def test_tjds_edge_cases(torch, case):
     x = rng.random(cols)
     ref = ob.csr_spmv(row_ptr, col_ind, val, x)
     y, ms, st = sm.tjds_compute(coo, rows, cols, iters=2, x=x)
-    assert_close(y, ref, row_scale(row_ptr, col_ind, val, x))
+    check_y(y, ref, row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
     y, ms, st = sm.csr_compute(coo, rows, cols, iters=2, x=x)
-    assert_close(y, ref, row_scale(row_ptr, col_ind, val, x))
+    check_y(y, ref, row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
 
 
 def test_create_rejects_malformed_arrays(torch):
@@ -1016,10 +1059,11 @@ def test_adopted_device_arrays(torch):
     row_ptr, col_ind, val = csr_from_lengths(rng, lens, 4000)
     x = rng.random(4000)
     A = sm.CsrMatrix(5000, 4000, dev(torch, row_ptr), dev(torch, col_ind), dev(torch, val))
-    dy = torch.empty(5000, dtype=torch.float64, device="cuda")
+    buf, dy = guarded_y(torch, 5000)
     A.spmv(dev(torch, x), dy)
     torch.cuda.synchronize()
-    assert_close(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x))
+    check_guards(buf, 5000)
+    check_y(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
 
 
 def test_runs_on_a_non_default_stream(torch):
@@ -1033,8 +1077,8 @@ def test_runs_on_a_non_default_stream(torch):
     for _ in range(5):
         A.spmv(dx, dy, stream=s)
     s.synchronize()
-    assert_close(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, np.ones(n)),
-                 row_scale(row_ptr, col_ind, val, np.ones(n)))
+    check_y(dy.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, np.ones(n)),
+            row_scale(row_ptr, col_ind, val, np.ones(n)), np.diff(row_ptr))
 
 
 # ------------------------------------------- full-size synthetic: properties only
@@ -1075,6 +1119,9 @@ def test_big_synthetic_properties(torch, big):
     k = 100_000
     sub = ob.csr_spmv(row_ptr[:k + 1].copy(), col_ind[:row_ptr[k]], val[:row_ptr[k]], xa.cpu().numpy())
     assert np.all(np.abs(ya.cpu().numpy()[:k] - sub) <= TOL * 2 * scale[:k])
+    # (4') and every row against the oracle: the binned plan's last row blocks, far rows and all
+    xa_h = xa.cpu().numpy()
+    check_y(ya.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, xa_h), row_scale(row_ptr, col_ind, val, xa_h), np.diff(row_ptr))
     # (5) idempotence: the same launch twice gives the same bits (no atomics on the CSR path) -- the plan AUTO picks for
     # this matrix (the binned one) and the tile kernel each repeat themselves; between them the normwise bound holds
     y2 = torch.empty_like(ya)
@@ -1109,11 +1156,11 @@ def test_reference_shaped_entry_points(torch, name):
     ref = ob.csr_spmv(row_ptr, col_ind, val, np.ones(n))
     scale = row_scale(row_ptr, col_ind, val, np.ones(n))
     y, ms, st = sm.csr_compute(coo, m, n, iters=20)
-    assert_close(y, ref, scale, exact=name in EXACT)
+    check_y(y, ref, scale, np.diff(row_ptr), exact=name in EXACT)
     assert len(ms) == 20 and np.all(ms > 0) and st.time_total == pytest.approx(ms.sum())
     assert st.time_min == ms.min() and st.time_max == ms.max() and st.time_stdev == pytest.approx(ms.std())
     y, ms, st = sm.tjds_compute(coo, m, n, iters=20)
-    assert_close(y, ref, scale, exact=name in EXACT)
+    check_y(y, ref, scale, np.diff(row_ptr), exact=name in EXACT)
     assert coo.tobytes() == before
 
 
@@ -1236,7 +1283,7 @@ def test_cli_ref_quirks_reproduces_reference_tjds_report(torch, tmp_path):
 
 # ------------------------------------------------------------- BASELINE config 4
 def test_uniform32_config4_shape(torch):
-    """10 M x 10 M, 32 uniform entries per row (BASELINE config 4) at 1/10 size: oracle on a slice + row sums."""
+    """10 M x 10 M, 32 uniform entries per row (BASELINE config 4) at 1/10 size: oracle on a slice and on every row + row sums."""
     M = 1_000_000
     row_ptr, col_ind, val = sm.synth_csr(sm.SYNTH_UNIFORM, 2024, M, M, param=32)
     x = np.random.default_rng(4).random(M)
@@ -1244,13 +1291,16 @@ def test_uniform32_config4_shape(torch):
     dx = dev(torch, x)
     scale = np.add.reduceat(np.abs(val * x[col_ind]), row_ptr[:-1])
     host = np.add.reduceat(val * x[col_ind], row_ptr[:-1])
+    ref_all, scale_all = ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x)
     for kernel, param in ((sm.CSR_KERNEL_STREAM, 0), (sm.CSR_KERNEL_VECTOR, 32), (sm.CSR_KERNEL_VECTOR, 64)):
         A.set_kernel(kernel, param)
-        dy = torch.full((M,), float("nan"), dtype=torch.float64, device="cuda")
+        buf, dy = guarded_y(torch, M)
         A.spmv(dx, dy)
         torch.cuda.synchronize()
+        check_guards(buf, M)
         y = dy.cpu().numpy()
         assert np.all(np.abs(y - host) <= TOL * scale)
+        check_y(y, ref_all, scale_all, 32)                                  # every row against the oracle
         k = 50_000
         ref = ob.csr_spmv(row_ptr[:k + 1].copy(), col_ind[:row_ptr[k]], val[:row_ptr[k]], x)
         assert np.all(np.abs(y[:k] - ref) <= TOL * scale[:k])
@@ -1512,11 +1562,12 @@ def test_entry_points_with_device_conversion(torch, name):
     ref = ob.csr_spmv(row_ptr, col_ind, val, np.ones(n))
     scale = row_scale(row_ptr, col_ind, val, np.ones(n))
     y, ms, st = sm.csr_compute(coo, m, n, iters=3, device_convert=True)
-    assert_close(y, ref, scale, exact=name in EXACT)
+    check_y(y, ref, scale, np.diff(row_ptr), exact=name in EXACT)
     y, ms, st = sm.tjds_compute(coo, m, n, iters=3, device_convert=True)
-    assert_close(y, ref, scale, exact=name in EXACT)
+    check_y(y, ref, scale, np.diff(row_ptr), exact=name in EXACT)
     y, ms, st = sm.tjds_compute(coo, m, n, iters=1, device_convert=True, ref_quirks=True)
-    assert_close(y, ob.tjds_spmv(ob.tjds_build(coo, m, n), np.ones(n), refquirks=True), scale, exact=name in EXACT)
+    check_y(y, ob.tjds_spmv(ob.tjds_build(coo, m, n), np.ones(n), refquirks=True), *refquirks_yardsticks(coo, m, n, np.ones(n)),
+            exact=name in EXACT)
 
 
 def test_cli_device_convert_flag(torch, tmp_path):
@@ -1556,13 +1607,13 @@ def test_single_process_sharded_products(torch, name, ngpus):
             ms = S.synchronize()
         assert ms > 0
         for slot in range(ngpus):                      # every GPU holds the whole gathered vector
-            assert_close(S.get_y(slot, gathered=True), ref, scale)
-        assert_close(S.get_y(0, gathered=False), ref, scale)
+            check_y(S.get_y(slot, gathered=True), ref, scale, np.diff(row_ptr))
+        check_y(S.get_y(0, gathered=False), ref, scale, np.diff(row_ptr))
         S.set_x(None)                                  # the reference's operand: ones
         S.spmv()
         S.synchronize()
-        assert_close(S.get_y(), ob.csr_spmv(row_ptr, col_ind, val, np.ones(n)),
-                     row_scale(row_ptr, col_ind, val, np.ones(n)), exact=name in EXACT)
+        check_y(S.get_y(), ob.csr_spmv(row_ptr, col_ind, val, np.ones(n)),
+                row_scale(row_ptr, col_ind, val, np.ones(n)), np.diff(row_ptr), exact=name in EXACT)
         S.close()
 
 
@@ -1588,13 +1639,13 @@ def test_sharded_chunks_and_both_exchange_forms(torch, chunks, balance, gather):
         for _ in range(2):
             S.spmv(allgather=gather, timed=True)
             assert S.synchronize() > 0
-        assert_close(S.get_y(0, gathered=True), ref, scale)
-        assert_close(S.get_y(0, gathered=False), ref, scale)
+        check_y(S.get_y(0, gathered=True), ref, scale, np.diff(row_ptr))
+        check_y(S.get_y(0, gathered=False), ref, scale, np.diff(row_ptr))
         if fmt == "csr":                                   # another kernel family on every chunk
             S.set_csr_kernel(sm.CSR_KERNEL_COLSWEEP, 1024)
             S.spmv(allgather=gather)
             S.synchronize()
-            assert_close(S.get_y(0, gathered=True), ref, scale)
+            check_y(S.get_y(0, gathered=True), ref, scale, np.diff(row_ptr))
         else:
             with pytest.raises(sm.SmvpError):
                 S.set_csr_kernel(sm.CSR_KERNEL_STREAM, 1024)
@@ -1635,7 +1686,7 @@ def test_sharded_unequal_blocks_on_several_gpus(torch, ngpus):
                 S.spmv(allgather=gather)
                 S.synchronize()
                 for slot in range(ngpus):
-                    assert_close(S.get_y(slot, gathered=True), ref, scale)
+                    check_y(S.get_y(slot, gathered=True), ref, scale, np.diff(row_ptr))
                 got[gather] = S.get_y(0, gathered=True)
                 S.close()
             assert np.array_equal(got[sm.GATHER_OVERLAPPED], got[sm.GATHER_AFTER])    # the same bits either way
@@ -1673,8 +1724,8 @@ def test_sharded_virtual_ranks_on_one_gpu(torch, ranks, push):
                     S.spmv(allgather=gather)
                 S.synchronize()
                 for slot in range(ranks):
-                    assert_close(S.get_y(slot, gathered=True), ref, scale)
-                assert_close(S.get_y(0, gathered=False), ref, scale)
+                    check_y(S.get_y(slot, gathered=True), ref, scale, np.diff(row_ptr))
+                check_y(S.get_y(0, gathered=False), ref, scale, np.diff(row_ptr))
                 got[gather] = S.get_y(ranks - 1, gathered=True)
                 info = S.exchange_info()
                 assert info["active"] == PUSH and set(info["available"]) == {sm.EXCHANGE_COPIES, sm.EXCHANGE_DIRECT} and info["rccl_ranks"] == 0
@@ -1692,7 +1743,7 @@ def test_sharded_virtual_ranks_on_one_gpu(torch, ranks, push):
                     S.set_csr_kernel(sm.CSR_KERNEL_COLSWEEP, 1024)      # zero-row chunks included
                     S.spmv(allgather=gather)
                     S.synchronize()
-                    assert_close(S.get_y(0, gathered=True), ref, scale)
+                    check_y(S.get_y(0, gathered=True), ref, scale, np.diff(row_ptr))
                 S.close()
             assert np.array_equal(got[sm.GATHER_OVERLAPPED], got[sm.GATHER_AFTER])    # the same bits either way
     # power iteration: the gathered y is the next operand on every rank
@@ -2118,7 +2169,7 @@ def test_fuzz_all_kernels_against_oracle(torch, seed):
     scale = row_scale(row_ptr, col_ind, val, x)
     for kernel, param in CSR_VARIANTS:
         y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, kernel, param)
-        assert_close(y, ref, scale)
+        check_y(y, ref, scale, np.diff(row_ptr))
     lens = np.diff(row_ptr)
     y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_STREAM, 0)
     assert np.array_equal(y[lens <= 32], ref[lens <= 32])          # short rows: the serial loop's bits
@@ -2130,11 +2181,12 @@ def test_fuzz_all_kernels_against_oracle(torch, seed):
         if mode == sm.TJDS_MODE_ROW_GATHER:
             T.set_tile((256, 1024, 2048)[seed % 3])
         T.set_x(dev(torch, x))
-        dy = torch.full((rows,), float("nan"), dtype=torch.float64, device="cuda")
+        buf, dy = guarded_y(torch, rows)
         T.zero_y(dy)
         T.spmv(dy)
         torch.cuda.synchronize()
-        assert_close(dy.cpu().numpy(), ref, scale)
+        check_guards(buf, rows)
+        check_y(dy.cpu().numpy(), ref, scale, np.diff(row_ptr))
         T.close()
     # device-built formats feed the same kernels
     d_coo = _coo_to_device(torch, coo)
@@ -2231,7 +2283,7 @@ def test_config4_full_size_properties(torch):
 
     AUTO picks the column sweep here.  Size-independent properties only: y(ones) = row sums (independent numpy
     computation), linearity, agreement of the sweep with the two tile kernels -- bit for bit, all three sum these rows in
-    serial order --, run-to-run bit equality, and the oracle on the first 20 000 rows."""
+    serial order --, run-to-run bit equality, and the oracle's bits on the first 20 000 rows and on all of them."""
     M = 10_000_000
     row_ptr, col_ind, val = sm.synth_csr(sm.SYNTH_UNIFORM, 2024, M, M, param=32)
     assert len(col_ind) == 320_000_000
@@ -2257,6 +2309,8 @@ def test_config4_full_size_properties(torch):
     k = 20_000
     ref = ob.csr_spmv(row_ptr[:k + 1].copy(), col_ind[:row_ptr[k]], val[:row_ptr[k]], xa.cpu().numpy())
     assert np.array_equal(ya.cpu().numpy()[:k], ref)        # ascending column order inside every row: the serial bits
+    # ... on all 10 M rows: the last generation of workgroups and the entries past 2^31 bytes of val against the oracle
+    check_y(ya.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, xa.cpu().numpy()), 0, 32, exact=True)
     for kernel in (sm.CSR_KERNEL_STREAM, sm.CSR_KERNEL_STREAM_CARRY):
         A.set_kernel(kernel, 0)
         A.spmv(xa, y2)
@@ -2299,9 +2353,9 @@ def test_gpu_y_against_committed_golden_vectors(torch, name):
     lens = np.diff(g["row_ptr"])
     assert np.array_equal(y[lens <= 32], g["y_csr"][lens <= 32])          # one lane, serial order: identical bits
     row_ptr, col_ind, val = sm.csr_from_coo(coo, m)
-    assert_close(y, g["y_csr"], row_scale(row_ptr, col_ind, val, np.ones(n)), exact=name in EXACT)
+    check_y(y, g["y_csr"], row_scale(row_ptr, col_ind, val, np.ones(n)), np.diff(row_ptr), exact=name in EXACT)
     yq, _, _ = sm.tjds_compute(coo, m, n, iters=1, ref_quirks=True)
-    assert_close(yq, g["y_tjds_refquirks"], row_scale(row_ptr, col_ind, val, np.ones(n)), exact=name in EXACT)
+    check_y(yq, g["y_tjds_refquirks"], *refquirks_yardsticks(coo, m, n, np.ones(n)), exact=name in EXACT)
 
 
 def test_products_can_be_captured_in_a_callers_graph(torch):
@@ -2338,7 +2392,7 @@ def test_products_can_be_captured_in_a_callers_graph(torch):
             torch.cuda.synchronize()
             g.replay()
             torch.cuda.synchronize()
-            assert_close(dy.cpu().numpy(), ob.csr_spmv(rp, ci, v, x), row_scale(rp, ci, v, x))
+            check_y(dy.cpu().numpy(), ob.csr_spmv(rp, ci, v, x), row_scale(rp, ci, v, x), np.diff(rp))
         del g
     A.close()
     T.close()
