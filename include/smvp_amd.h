@@ -169,7 +169,8 @@ int smvp_device_info(int device, char *name, size_t name_cap, int *compute_units
  * the same result from run to run, bit for bit.
  * COLSWEEP, BINNED, the 16-bit column offsets of STREAM and the TJDS value cache keep (parts of) the entries a
  * second time, copied when the plan is built: a handle over adopted device arrays (SMVP_MEM_DEVICE) whose
- * val / col_ind are then changed in place must be re-planned (smvp_csr_set_kernel) or re-created. */
+ * val / col_ind are then changed in place must be re-planned (smvp_csr_set_kernel) or re-created.  (smvp_csr_spmm keeps no
+ * second copy: its plan depends on row_ptr alone, and it reads val / col_ind themselves.) */
 enum {
     SMVP_CSR_KERNEL_AUTO = 0,
     SMVP_CSR_KERNEL_VECTOR = 1,      /* one (sub-)wavefront per row, __shfl_down sums */
@@ -267,6 +268,29 @@ typedef struct smvp_plan_info {
     double build_ms;
 } smvp_plan_info_t;
 int smvp_csr_plan_info(const smvp_csr_t *h, smvp_plan_info_t *out);
+/* k products that share one read of the matrix (new: the reference multiplies by one x, main-cli.c:410-416):
+ *   d_Y[r*ldy + v] = sum_{j in row r} val[j] * d_X[col_ind[j]*ldx + v]     r < rows, v < k
+ * X is cols x k and Y rows x k, both row-major doubles with leading dimensions ldx >= k, ldy >= k (a contiguous (n, k) array,
+ * or a slice of columns of a wider one; column-major operands are not supported).
+ *   - Bits: every Y(r, v) is bit for bit the serial loop on column v -- acc = 0.0; for j in row_ptr[r] .. row_ptr[r+1]:
+ *     acc += val[j] * X(col_ind[j], v), each product rounded before the add -- for every row length, k, ldx, ldy, whatever
+ *     SpMV plan the handle holds, on every stream and after any history of calls.  (Stronger than smvp_csr_spmv, whose
+ *     default kernel keeps the serial order only on rows of up to 32 entries.)
+ *   - Writes: Y(r, v) for v < k is overwritten (an empty row gets +0.0; no pre-zeroing); Y(r, v) for k <= v < ldy is never
+ *     touched.
+ *   - The matrix is read once per 16 vectors: ceil(k / 16) passes.
+ *   - SMVP_ERR_INVALID, before anything is enqueued, for: a NULL handle; k < 1, ldx < k or ldy < k; a NULL d_X with nnz > 0
+ *     or a NULL d_Y with rows > 0; byte ranges of X and Y that overlap; a capturing stream on a handle whose SpMM plan is not
+ *     built yet (make one call outside the capture first, as for the SpMV plans).  SMVP_ERR_UNSUPPORTED for a handle that is
+ *     not plain CSR.
+ *   - Asynchronous on `stream`.  The first call on a handle builds the SpMM plan (one int per row, from row_ptr alone) and
+ *     synchronises `stream`.  With adopted arrays (SMVP_MEM_DEVICE), val / col_ind changed in place are seen by the next call
+ *     without a re-plan. */
+int smvp_csr_spmm(smvp_csr_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream);
+/* The kernel symbols of a product with k vectors (one per pass), its algorithmic bytes 12 nnz + 4 (rows + 1) + 8 k (cols + rows)
+ * (SURVEY 8(d) with k operands, whatever the number of passes), and in `plan` (may be NULL) the SpMM plan's bytes and build
+ * time -- zero until the first smvp_csr_spmm.  smvp_csr_plan_info keeps describing the SpMV plan only. */
+int smvp_csr_spmm_describe(const smvp_csr_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes, smvp_plan_info_t *plan);
 void smvp_csr_destroy(smvp_csr_t *h);
 
 /* Device-side half of smvp_tjds_compute (main-cli.c:756-763,944-967): val,

@@ -178,6 +178,11 @@ struct smvp_csr {
     bool plain_only = false;   // a nested handle: AUTO stays on the tile kernels
     int sweep_g = 0;           // COLSWEEP: chunks in flight per wavefront (fixed when the plan is built)
     double plan_build_ms = 0.0;  // host wall time of the last plan build
+    // smvp_csr_spmm (K7, smvp_spmm.hip): the rows ordered by length inside blocks of kSpmmBlockRows, built by the first call
+    // and kept whatever the SpMV plan is (it depends on row_ptr only)
+    int *d_spmm_order = nullptr;
+    bool spmm_planned = false;
+    double spmm_build_ms = 0.0;
 };
 
 namespace {
@@ -1111,6 +1116,67 @@ extern "C" int smvp_csr_plan_info(const smvp_csr_t *h, smvp_plan_info_t *out)
     return SMVP_OK;
 }
 
+// K7: every argument is checked before anything is enqueued; the first call builds the plan (and synchronises `stream`)
+extern "C" int smvp_csr_spmm(smvp_csr_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: null handle");
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_spmm: plain CSR handles only (this one belongs to a TJDS matrix)");
+    if (k < 1 || ldx < k || ldy < k)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: k = %d, ldx = %lld, ldy = %lld (need k >= 1, ldx >= k, ldy >= k)", k, ldx, ldy);
+    if ((h->nnz > 0 && !d_X) || (h->rows > 0 && !d_Y))
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: null %s", h->rows > 0 && !d_Y ? "d_Y" : "d_X");
+    // the byte ranges the operands span: X(c, v) for c < cols, Y(r, v) for r < rows (v < k)
+    const unsigned __int128 xa = (uintptr_t)d_X, ya = (uintptr_t)d_Y;
+    const unsigned __int128 xb = xa + ((unsigned __int128)(h->cols > 0 ? h->cols - 1 : 0) * (unsigned long long)ldx + (unsigned)k) * 8u;
+    const unsigned __int128 yb = ya + ((unsigned __int128)(h->rows > 0 ? h->rows - 1 : 0) * (unsigned long long)ldy + (unsigned)k) * 8u;
+    if (d_X && d_Y && h->cols > 0 && h->rows > 0 && xa < yb && ya < xb)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: the byte ranges of d_X and d_Y overlap");
+    DeviceScope on(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->spmm_planned) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing(st, &cs));
+        if (cs != hipStreamCaptureStatusNone)
+            return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: the first call on a handle builds its plan and cannot be captured "
+                                                "(call it once outside the capture)");
+        const double t0 = wall_ms();
+        if (h->rows > 0 && !h->d_spmm_order && hipMalloc((void **)&h->d_spmm_order, sizeof(int) * (size_t)h->rows) != hipSuccess) {
+            h->d_spmm_order = nullptr;
+            return smvp::fail(SMVP_ERR_ALLOC, "smvp_csr_spmm: cannot allocate the plan (%d rows)", h->rows);
+        }
+        if (int rc = smvp::build_spmm_order(h->d_row_ptr, h->rows, h->max_row_len, h->d_spmm_order, st))
+            return rc;
+        h->spmm_planned = true;
+        h->spmm_build_ms = wall_ms() - t0;
+    }
+    const hipError_t e = smvp::launch_csr_spmm(h->d_row_ptr, h->d_col_ind, h->d_val, h->d_spmm_order, d_X, ldx, d_Y, ldy, h->rows, k, st);
+    if (e != hipSuccess)
+        return smvp::fail(SMVP_ERR_HIP, "smvp_csr_spmm: launch failed: %s", hipGetErrorString(e));
+    return SMVP_OK;
+}
+
+extern "C" int smvp_csr_spmm_describe(const smvp_csr_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes, smvp_plan_info_t *plan)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm_describe: null handle");
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_spmm_describe: plain CSR handles only");
+    if (k < 1)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm_describe: k = %d (need k >= 1)", k);
+    if (kernel_name && cap)
+        smvp::spmm_kernel_name(k, kernel_name, cap);
+    if (alg_bytes)
+        *alg_bytes = 12.0 * h->nnz + 4.0 * (h->rows + 1.0) + 8.0 * k * ((double)h->cols + h->rows);
+    if (plan) {
+        plan->matrix_bytes = 12.0 * h->nnz + 4.0 * (h->rows + 1.0);
+        plan->plan_bytes = h->spmm_planned ? 4.0 * h->rows : 0.0;
+        plan->build_ms = h->spmm_planned ? h->spmm_build_ms : 0.0;
+    }
+    return SMVP_OK;
+}
+
 extern "C" void smvp_csr_destroy(smvp_csr_t *h)
 {
     if (!h)
@@ -1121,6 +1187,8 @@ extern "C" void smvp_csr_destroy(smvp_csr_t *h)
     free_stream_plan(h);
     free_sweep_plan(h);
     free_binned(h);
+    if (h->d_spmm_order)
+        (void)hipFree(h->d_spmm_order);
     if (h->own_row_ptr && h->d_row_ptr)
         (void)hipFree(h->d_row_ptr);
     if (h->own_col_ind && h->d_col_ind)

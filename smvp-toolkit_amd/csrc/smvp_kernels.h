@@ -20,6 +20,22 @@ constexpr int kSweepTurnCap = (1 << (16 - kSweepRowBits)) - 1;  // ... and the 1
 constexpr int kTjdsBlock = 256;     // permuted columns per work item
 constexpr int kTjdsDiagChunk = 8;   // jagged diagonals per work item
 
+// Blocks are dealt round-robin over the 8 XCDs; XCD i takes `group` consecutive tiles out of every run of 8 * group
+// (the measurements are beside K2 in smvp_kernels.hip)
+__device__ __forceinline__ int tile_of_block(int block, int group)
+{
+    const int xcd = block & 7, seq = block >> 3;
+    return (seq / group) * (8 * group) + xcd * group + seq % group;
+}
+
+// K7 (smvp_spmm.hip): k products that share one read of the matrix
+constexpr int kSpmmMaxVectors = 16;    // vectors per pass (16 doubles: one 128-byte line of X per gathered column)
+constexpr int kSpmmBlockRows = 4096;   // the plan orders rows by length inside blocks of this many consecutive rows
+int build_spmm_order(const int *row_ptr, int rows, int longest_row, int *order, hipStream_t stream);  // SMVP status
+hipError_t launch_csr_spmm(const int *row_ptr, const int *col_ind, const double *val, const int *order, const double *X,
+                           long long ldx, double *Y, long long ldy, int rows, int k, hipStream_t stream);
+void spmm_kernel_name(int k, char *name, size_t cap);  // the passes' kernel symbols
+
 hipError_t launch_csr_vector(int lanes_per_row, const int *row_ptr, const int *col_ind, const double *val,
                              const double *x, double *y, int rows, hipStream_t stream);
 hipError_t launch_csr_stream(int vpt, const int *row_ptr, const int *col_ind, const double *val,

@@ -41,12 +41,8 @@ __device__ __forceinline__ double shfl_down_sum(double v)
 //   group 32    65.2 / 21.2   1.84 GB      group 2048  55.9 / 20.8   1.60 GB
 // (one XCD per contiguous eighth of the matrix was 60.1 %).  64 keeps the speed of
 // the small groups and most of the traffic saving of the large ones.
-// Speed only: any placement gives the same result.
-__device__ __forceinline__ int tile_of_block(int block, int group)
-{
-    const int xcd = block & 7, seq = block >> 3;
-    return (seq / group) * (8 * group) + xcd * group + seq % group;
-}
+// Speed only: any placement gives the same result.  (tile_of_block itself lives in
+// smvp_kernels.h: K7, smvp_spmm.hip, deals its row blocks the same way.)
 
 #ifndef SMVP_TU_ILP
 // ---------------------------------------------------------------------------

@@ -109,7 +109,7 @@ EXPORTS = [
     "smvp_csr_from_coo", "smvp_tjds_from_coo", "smvp_csr_from_coo_device", "smvp_tjds_from_coo_device",
     "smvp_device_count", "smvp_device_info", "smvp_csr_plan_info", "smvp_tjds_plan_info",
     "smvp_csr_create", "smvp_csr_create_block", "smvp_csr_far_share", "smvp_csr_set_kernel", "smvp_csr_get_kernel", "smvp_csr_gather_spread", "smvp_csr_spmv",
-    "smvp_csr_describe", "smvp_csr_plan_launches", "smvp_csr_destroy",
+    "smvp_csr_describe", "smvp_csr_plan_launches", "smvp_csr_destroy", "smvp_csr_spmm", "smvp_csr_spmm_describe",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -147,6 +147,8 @@ def lib():
         L.smvp_tjds_plan_info.argtypes = [vp, C.POINTER(PlanInfo)]
         L.smvp_csr_destroy.argtypes = [vp]
         L.smvp_csr_destroy.restype = None
+        L.smvp_csr_spmm.argtypes = [vp, ci, vp, C.c_longlong, vp, C.c_longlong, vp]
+        L.smvp_csr_spmm_describe.argtypes = [vp, ci, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(PlanInfo)]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -438,6 +440,27 @@ def _stream_ptr(stream):
     return C.c_void_p(stream.cuda_stream)   # torch.cuda.Stream
 
 
+def spmm_operands(X, Y, rows, cols):
+    """(k, ldx, ldy) of the operands of CsrMatrix.spmm: X of shape (cols, k) and Y of shape (rows, k), float64 tensors whose
+    rows are contiguous (stride(1) == 1; the leading dimension is stride(0) >= k).  Raises ValueError otherwise.  Checks
+    shapes and strides only, so it runs on CPU tensors too."""
+    for name, t, n in (("X", X, cols), ("Y", Y, rows)):
+        if not hasattr(t, "stride") or not hasattr(t, "dim") or t.dim() != 2:
+            raise ValueError("%s must be a 2-D tensor" % name)
+        if str(t.dtype) != "torch.float64":
+            raise ValueError("%s must be float64, not %s" % (name, t.dtype))
+        if t.shape[0] != n:
+            raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.shape[0], n))
+    k = X.shape[1]
+    if k < 1 or Y.shape[1] != k:
+        raise ValueError("X and Y need the same number of columns k >= 1 (X has %d, Y %d)" % (X.shape[1], Y.shape[1]))
+    for name, t in (("X", X), ("Y", Y)):
+        if t.stride(1) != 1 or t.stride(0) < k:
+            raise ValueError("%s must be row-major with contiguous rows (stride(1) == 1, stride(0) >= k); its strides are %s"
+                             % (name, tuple(t.stride())))
+    return k, X.stride(0), Y.stride(0)
+
+
 class CsrMatrix:
     """Device-resident CSR matrix (smvp_csr_t).  Arrays may be numpy (copied to HBM) or torch CUDA tensors (adopted)."""
 
@@ -500,6 +523,23 @@ class CsrMatrix:
         b = C.c_double()
         _check(lib().smvp_csr_describe(self._h, name, 256, C.byref(b)), "smvp_csr_describe")
         return name.value.decode(), b.value
+
+    def spmm(self, X, Y, stream=None):
+        """Y = A X for k vectors at once (smvp_csr_spmm): X (cols x k) and Y (rows x k) are float64 CUDA tensors with
+        stride(1) == 1, ldx = X.stride(0), ldy = Y.stride(0).  Every column of Y is the serial loop's bits.  Asynchronous on
+        `stream`; the first call builds the plan."""
+        k, ldx, ldy = spmm_operands(X, Y, self.rows, self.cols)
+        if not (X.is_cuda and Y.is_cuda):
+            raise ValueError("X and Y must be device tensors")
+        _check(lib().smvp_csr_spmm(self._h, k, _dev_ptr(X), ldx, _dev_ptr(Y), ldy, _stream_ptr(stream)), "smvp_csr_spmm")
+
+    def spmm_describe(self, k):
+        """(kernel symbols, algorithmic bytes for k vectors, {plan_bytes, build_ms} of the SpMM plan: 0 before the first spmm)."""
+        name = C.create_string_buffer(256)
+        b = C.c_double()
+        i = PlanInfo()
+        _check(lib().smvp_csr_spmm_describe(self._h, k, name, 256, C.byref(b), C.byref(i)), "smvp_csr_spmm_describe")
+        return name.value.decode(), b.value, {"plan_bytes": i.plan_bytes, "build_ms": i.build_ms}
 
     def close(self):
         if self._h:
