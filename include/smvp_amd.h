@@ -148,7 +148,8 @@ int smvp_tjds_from_coo(const smvp_coo_t *coo, int rows, int cols, int nnz,
 /* The same two conversions on the GPU (next row of SURVEY 8(f)): every pointer is a device
  * address, outputs are bit-identical to the host versions above.  Radix sort + scans instead of
  * the reference's qsorts and its O(nnz * cols) renumbering (main-cli.c:894-904).  Both return
- * after the work on `stream` has finished. */
+ * after the work on `stream` has finished.  Like smvp_csr_create and smvp_tjds_create they take at
+ * most 2^31 - 1 - 65536 = 2 147 418 111 entries (SMVP_ERR_UNSUPPORTED above, before any work). */
 int smvp_csr_from_coo_device(const smvp_coo_t *d_coo, int rows, int cols, int nnz,
                              int *d_row_ptr, int *d_col_ind, double *d_val, void *stream);
 int smvp_tjds_from_coo_device(const smvp_coo_t *d_coo, int rows, int cols, int nnz,
@@ -226,7 +227,8 @@ typedef struct smvp_csr smvp_csr_t;   /* device-resident CSR matrix + launch pla
 typedef struct smvp_tjds smvp_tjds_t; /* device-resident TJDS matrix + launch plan */
 
 /* Device-side half of smvp_csr_compute (main-cli.c:343-370): the three arrays
- * live in HBM, laid out exactly as CSRData (main-cli.c:61-66).  row_ptr is
+ * live in HBM, laid out exactly as CSRData (main-cli.c:61-66).  At most 2^31 - 1 - 65536 =
+ * 2 147 418 111 entries (smvp_tjds_create too): more is SMVP_ERR_UNSUPPORTED.  row_ptr is
  * always read from the host copy as well to build the launch plan, so with
  * SMVP_MEM_DEVICE pass the host row_ptr in `host_row_ptr` (NULL = copy it back). */
 int smvp_csr_create(smvp_csr_t **out, int device, int rows, int cols, int nnz,

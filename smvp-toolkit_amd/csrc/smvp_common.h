@@ -6,6 +6,10 @@
 #include <cstdio>
 
 namespace smvp {
+// The most entries a matrix may have (smvp_csr_create, smvp_tjds_create and the device-side converters): 32-bit indices like
+// the reference's; the kernels and plan builders add up to a few thousand to an entry index and round grids up to whole tiles
+constexpr long long kMaxEntries = 2147483647ll - 65536;
+
 // Records a message for smvp_last_error() and hands back `code`.
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void clear_error();

@@ -694,6 +694,9 @@ extern "C" int smvp_csr_from_coo_device(const smvp_coo_t *d_coo, int rows, int c
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_from_coo_device: bad argument");
     if (nnz > 0 && (rows == 0 || cols == 0))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_from_coo_device: entries in an empty matrix");
+    if (nnz > smvp::kMaxEntries)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_from_coo_device: %d entries: more than the %lld a matrix may hold", nnz,
+                          smvp::kMaxEntries);
     if (int rc = check_device(d_coo, "smvp_csr_from_coo_device"))
         return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -721,6 +724,9 @@ extern "C" int smvp_tjds_from_coo_device(const smvp_coo_t *d_coo, int rows, int 
         return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_from_coo_device: bad argument");
     if (nnz > 0 && (rows == 0 || cols == 0))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_from_coo_device: entries in an empty matrix");
+    if (nnz > smvp::kMaxEntries)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_from_coo_device: %d entries: more than the %lld a matrix may hold", nnz,
+                          smvp::kMaxEntries);
     if (int rc = check_device(d_coo, "smvp_tjds_from_coo_device"))
         return rc;
     hipStream_t st = (hipStream_t)stream;

@@ -42,8 +42,7 @@ struct DeviceScope {
     }
 };
 
-// 32-bit indices like the reference's; the kernels add up to a few thousand to an entry index
-constexpr long long kMaxEntries = 2147483647ll - 65536;
+using smvp::kMaxEntries;
 
 int usable_device(int device)
 {

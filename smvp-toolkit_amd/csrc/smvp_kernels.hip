@@ -13,6 +13,7 @@
 // by one lane is bit-identical to the serial CPU result.
 #include "smvp_kernels.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
@@ -54,10 +55,10 @@ __device__ __forceinline__ double shfl_down_sum(double v)
 template <int T>
 __global__ __launch_bounds__(kVectorBlock) void csr_vector_rows(
     const int *__restrict__ row_ptr, const int *__restrict__ col_ind, const double *__restrict__ val,
-    const double *__restrict__ x, double *__restrict__ y, int rows)
+    const double *__restrict__ x, double *__restrict__ y, int rows, int row0)
 {
     const long long gid = (long long)blockIdx.x * kVectorBlock + threadIdx.x;
-    const long long row = gid / T;
+    const long long row = row0 + gid / T;  // (launched in row chunks: a grid holds fewer than 2^32 threads)
     const int lane = threadIdx.x & (T - 1);
     int a = 0, z = 0;
     if (row < rows) {
@@ -1089,17 +1090,15 @@ __global__ __launch_bounds__(256) void fill_value(double *__restrict__ p, double
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-hipError_t launch_csr_vector(int lanes_per_row, const int *row_ptr, const int *col_ind, const double *val,
-                             const double *x, double *y, int rows, hipStream_t stream)
+// rows [row0, row0 + n) of the vector kernel: one launch of n * lanes_per_row threads
+static hipError_t launch_csr_vector_rows(int lanes_per_row, const int *row_ptr, const int *col_ind, const double *val,
+                                         const double *x, double *y, int rows, int row0, int n, hipStream_t stream)
 {
-    if (rows <= 0)
-        return hipSuccess;
-    const long long threads = (long long)rows * lanes_per_row;
-    const unsigned grid = (unsigned)((threads + kVectorBlock - 1) / kVectorBlock);
+    const unsigned grid = (unsigned)(((long long)n * lanes_per_row + kVectorBlock - 1) / kVectorBlock);
 #define SMVP_VEC_CASE(T)                                                                              \
     case T:                                                                                           \
         hipLaunchKernelGGL(csr_vector_rows<T>, dim3(grid), dim3(kVectorBlock), 0, stream, row_ptr,   \
-                           col_ind, val, x, y, rows);                                                 \
+                           col_ind, val, x, y, rows, row0);                                           \
         break;
     switch (lanes_per_row) {
         SMVP_VEC_CASE(2)
@@ -1113,6 +1112,24 @@ hipError_t launch_csr_vector(int lanes_per_row, const int *row_ptr, const int *c
     }
 #undef SMVP_VEC_CASE
     return hipGetLastError();
+}
+
+hipError_t launch_csr_vector(int lanes_per_row, const int *row_ptr, const int *col_ind, const double *val,
+                             const double *x, double *y, int rows, hipStream_t stream)
+{
+    if (lanes_per_row < 1)
+        return hipErrorInvalidValue;
+    // at most 2^31 threads per launch (a multiple of the block): 32 or 64 lanes for each of 2^27 rows would pass the 2^32
+    // threads a grid may hold
+    const int chunk = (int)(((long long)1 << 31) / lanes_per_row);
+    for (int row0 = 0; row0 < rows; row0 += chunk) {
+        const int n = std::min(chunk, rows - row0);
+        if (hipError_t e = launch_csr_vector_rows(lanes_per_row, row_ptr, col_ind, val, x, y, rows, row0, n, stream))
+            return e;
+        if (rows - row0 <= chunk)
+            break;  // (row0 + chunk may not fit an int)
+    }
+    return hipSuccess;
 }
 
 // Tiles per XCD turn for a launch of `ntiles` tiles: kStreamTileGroup, smaller for small matrices so that

@@ -25,6 +25,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 SYNTH_MEMPLUS_SHAPED, SYNTH_UNIFORM = 1, 2
 TJDS_MODE_AUTO, TJDS_MODE_ATOMIC, TJDS_MODE_TWO_PHASE, TJDS_MODE_ROW_GATHER = 0, 1, 2, 3
 TIMING_AUTO, TIMING_EVENTS, TIMING_DEVICE, TIMING_DEVICE_GRAPH = 0, 1, 2, 3
+MAX_ENTRIES = 2 ** 31 - 1 - 65536   # the most entries a matrix may hold (include/smvp_amd.h): more is ERR_UNSUPPORTED
 
 COO_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("val", "<f8")], align=True)
 
@@ -92,10 +93,17 @@ EXCHANGE_NAMES = {EXCHANGE_RCCL: "rccl", EXCHANGE_COPIES: "copies", EXCHANGE_DIR
 
 
 class SmvpError(RuntimeError):
-    def __init__(self, code, where):
+    def __init__(self, code, where, msg=None):
         self.code = code
-        msg = lib().smvp_last_error().decode(errors="replace")
+        if msg is None:
+            msg = lib().smvp_last_error().decode(errors="replace")
         super().__init__("%s failed with status %d: %s" % (where, code, msg))
+
+
+def _check_entries(nnz, where):
+    """The library's limit on the entries of a matrix, checked before a wrapper allocates outputs for them."""
+    if nnz > MAX_ENTRIES:
+        raise SmvpError(ERR_UNSUPPORTED, where, "%d entries: more than the %d a matrix may hold" % (nnz, MAX_ENTRIES))
 
 
 _lib = None
@@ -343,6 +351,8 @@ def csr_from_coo_device(d_coo, rows, cols, nnz, stream=None):
     Returns (row_ptr, col_ind, val) as torch CUDA tensors."""
     import torch
 
+    _check_entries(nnz, "smvp_csr_from_coo_device")
+
     row_ptr = torch.empty(rows + 1, dtype=torch.int32, device=d_coo.device)
     col_ind = torch.empty(max(nnz, 1), dtype=torch.int32, device=d_coo.device)
     val = torch.empty(max(nnz, 1), dtype=torch.float64, device=d_coo.device)
@@ -354,6 +364,8 @@ def csr_from_coo_device(d_coo, rows, cols, nnz, stream=None):
 def tjds_from_coo_device(d_coo, rows, cols, nnz, stream=None):
     """COO -> TJDS on the GPU -> TjdsArrays whose arrays are torch CUDA tensors."""
     import torch
+
+    _check_entries(nnz, "smvp_tjds_from_coo_device")
 
     t = TjdsArrays()
     t.rows, t.cols, t.nnz = rows, cols, nnz

@@ -127,6 +127,14 @@ def binned_regime(row_ptr, col_ind, cols, band=0, row0=0):
     return out
 
 
+def binned_fits(nf, cols):
+    """Whether build_binned_plan takes a matrix with nf far entries (binned_regime's nf: after the row cap) and `cols` columns:
+    its streams of far products are addressed with 32-bit positions, nf plus up to 256 of padding for every column block,
+    every row block and two more, and it refuses with SMVP_ERR_UNSUPPORTED where that passes 2147483000 (smvp_binned.hip)."""
+    ncb = -(-int(cols) // (1 << BIN_COL_BITS))
+    return int(nf) + 256 * (ncb + int(nf) // BIN_BUCKET + 2) <= 2147483000
+
+
 SPILL_KINDS = ("cells", "runs", "fr32")
 
 
