@@ -171,7 +171,8 @@ int smvp_device_info(int device, char *name, size_t name_cap, int *compute_units
  * COLSWEEP, BINNED, the 16-bit column offsets of STREAM and the TJDS value cache keep (parts of) the entries a
  * second time, copied when the plan is built: a handle over adopted device arrays (SMVP_MEM_DEVICE) whose
  * val / col_ind are then changed in place must be re-planned (smvp_csr_set_kernel) or re-created.  (smvp_csr_spmm keeps no
- * second copy: its plan depends on row_ptr alone, and it reads val / col_ind themselves.) */
+ * second copy: its plan depends on row_ptr alone, and it reads val / col_ind themselves.)  A handle made by
+ * smvp_csr_create_transposed is a second copy of all the entries: after such a change it is stale and must be created again. */
 enum {
     SMVP_CSR_KERNEL_AUTO = 0,
     SMVP_CSR_KERNEL_VECTOR = 1,      /* one (sub-)wavefront per row, __shfl_down sums */
@@ -293,6 +294,30 @@ int smvp_csr_spmm(smvp_csr_t *h, int k, const double *d_X, long long ldx, double
  * (SURVEY 8(d) with k operands, whatever the number of passes), and in `plan` (may be NULL) the SpMM plan's bytes and build
  * time -- zero until the first smvp_csr_spmm.  smvp_csr_plan_info keeps describing the SpMV plan only. */
 int smvp_csr_spmm_describe(const smvp_csr_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes, smvp_plan_info_t *plan);
+/* ------------------------------------------------------------ transposed product */
+/* y = A^T x (new: the reference multiplies by A only).  For an M x N matrix, x of M doubles, y of N doubles:
+ *     y[c] = acc,  acc = 0.0;  for every stored entry (r, c) of column c, in ascending r, entries with equal (r, c) in storage
+ *                              order:  acc += val * x[r]      (each product rounded before the add, -ffp-contract=off)
+ * i.e. the serial loop of main-cli.c:410-416 run over the CSR arrays of A^T as smvp_csr_from_coo builds them from the entries
+ * with row and column swapped.  A column without entries gets +0.0; y is fully overwritten (no pre-zeroing).  "Storage order" is
+ * the TJDS position for a TJDS handle and the CSR position for a CSR handle; for arrays built by this library's converters from
+ * one COO list the two are the same order, and both routes below give the same bits.
+ *
+ * Route 1, smvp_csr_create_transposed: A^T as an ordinary CSR handle, built on the device.  *out is a new, independent plain-CSR
+ * handle of the N x M matrix A^T on h's device: it owns its three arrays, holds a host copy of its row_ptr, starts on AUTO and
+ * outlives h; everything a CSR handle offers works on it (smvp_csr_spmv, smvp_csr_set_kernel, smvp_csr_spmm, ...).  Its rows
+ * have ascending columns (= ascending rows of A), ties in h's storage order: bit for bit smvp_csr_from_coo of the swapped
+ * entries, whatever order h's col_ind has inside a row.  The entries are written as a COO list (16 B per entry), sorted by
+ * smvp_csr_from_coo_device and adopted; the list and the sort's buffers are freed before the call returns, and it returns after
+ * the work on `stream` has finished.  A row block (smvp_csr_create_block) is accepted: the result is a whole-matrix handle
+ * whose columns are the block's local rows.  SMVP_ERR_INVALID for a NULL handle / out or a capturing stream (nothing is
+ * enqueued; the capture stays valid); SMVP_ERR_UNSUPPORTED for a handle that is not plain CSR; SMVP_ERR_ALLOC when memory runs
+ * out (nothing leaked).  *out is NULL after every failure.  It is a second copy in the sense of the note at SMVP_CSR_KERNEL_*:
+ * after val / col_ind of adopted arrays (SMVP_MEM_DEVICE) are changed in place, the transposed handle is stale -- create it again. */
+int smvp_csr_create_transposed(smvp_csr_t **out, const smvp_csr_t *h, void *stream);
+/* The device addresses a plain-CSR handle multiplies from (its own copies, or the adopted arrays), valid until the handle is
+ * destroyed; NULL outputs are skipped.  SMVP_ERR_UNSUPPORTED for a handle that is not plain CSR. */
+int smvp_csr_device_arrays(const smvp_csr_t *h, const int **d_row_ptr, const int **d_col_ind, const double **d_val);
 void smvp_csr_destroy(smvp_csr_t *h);
 
 /* Device-side half of smvp_tjds_compute (main-cli.c:756-763,944-967): val,
@@ -344,6 +369,19 @@ int smvp_tjds_get_value_cache(const smvp_tjds_t *h, int *min_tiles, long long *c
 int smvp_tjds_set_ref_quirks(smvp_tjds_t *h, int enable, int ref_num_tjdiag, int last_diag_single);
 int smvp_tjds_describe(const smvp_tjds_t *h, char *kernel_name, size_t cap, double *alg_bytes);
 int smvp_tjds_plan_info(const smvp_tjds_t *h, smvp_plan_info_t *out); /* plan: x_perm, the work items, the selected modes' plans */
+/* Route 2 of the transposed product (definition above smvp_csr_create_transposed), kernel K8: d_y[0..cols) = A^T * d_x[0..rows)
+ * from the handle's own val / row_ind / start_pos / perm -- TJDS stores A by columns, so permuted column k is a row of A^T and
+ * one lane sums it from top to bottom.  No second copy, no plan, no atomics; asynchronous on `stream` and capturable into a
+ * hipGraph from the first call.  Every y[c] is the definition's bits for every column length, the same on every run.  It reads
+ * neither the permuted operand of smvp_tjds_set_x nor any mode's plan: the result does not depend on smvp_tjds_set_mode /
+ * set_tile / set_value_cache / set_ref_quirks, and a forward smvp_tjds_spmv after it gives the bits it gave before it without
+ * a new smvp_tjds_set_x.  A column is walked by one lane however long it is (as smvp_csr_spmm walks a row).
+ * SMVP_ERR_INVALID, before anything is enqueued, for: a NULL handle; a NULL d_x with nnz > 0; a NULL d_y with cols > 0; byte
+ * ranges of x and y that overlap. */
+int smvp_tjds_spmv_transposed(smvp_tjds_t *h, const double *d_x, double *d_y, void *stream);
+/* Its kernel symbol and algorithmic bytes 12 nnz + 4 (D + 1) + 4 cols + 8 rows + 8 cols (SURVEY 8(d)'s TJDS figure with x and y
+ * changing places, plus perm, which this product reads once where the forward one reads the permuted operand). */
+int smvp_tjds_transposed_describe(const smvp_tjds_t *h, char *kernel_name, size_t cap, double *alg_bytes);
 void smvp_tjds_destroy(smvp_tjds_t *h);
 
 /* ------------------------------------------- several GPUs, one host process */

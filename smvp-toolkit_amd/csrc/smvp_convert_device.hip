@@ -687,6 +687,50 @@ int build_row_gather_plan(const int *d_row_ind, const int *d_start_pos, int num_
 
 }  // namespace smvp
 
+namespace {
+
+// entry j of a CSR matrix as the entry of the transposed matrix: {row = col_ind[j], col = the row that holds j, val[j]}, in
+// storage order (smvp_csr_create_transposed).  The row is the last r with row_ptr[r] <= j: empty rows share their
+// neighbour's row_ptr and are passed over.
+__global__ __launch_bounds__(256) void csr_swapped_coo(const int *__restrict__ row_ptr, const int *__restrict__ col_ind,
+                                                       const double *__restrict__ val, int rows, long long nnz,
+                                                       smvp_coo_t *__restrict__ coo)
+{
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < nnz; j += stride) {
+        int lo = 0, hi = rows;  // row_ptr[lo] <= j < row_ptr[hi]
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            if (row_ptr[mid] <= j)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        smvp_coo_t e;
+        e.row = col_ind[j];
+        e.col = lo;
+        e.val = val[j];
+        coo[j] = e;
+    }
+}
+
+}  // namespace
+
+namespace smvp {
+
+hipError_t launch_csr_swapped_coo(const int *row_ptr, const int *col_ind, const double *val, int rows, int nnz, smvp_coo_t *coo,
+                                  hipStream_t st)
+{
+    if (nnz <= 0 || rows <= 0)
+        return hipSuccess;
+    const long long blocks = ((long long)nnz + 255) / 256;
+    hipLaunchKernelGGL(csr_swapped_coo, dim3((unsigned)std::min<long long>(blocks, 1 << 20)), dim3(256), 0, st, row_ptr, col_ind,
+                       val, rows, (long long)nnz, coo);
+    return hipGetLastError();
+}
+
+}  // namespace smvp
+
 extern "C" int smvp_csr_from_coo_device(const smvp_coo_t *d_coo, int rows, int cols, int nnz,
                                         int *d_row_ptr, int *d_col_ind, double *d_val, void *stream)
 {

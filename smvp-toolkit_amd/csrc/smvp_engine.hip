@@ -1176,6 +1176,82 @@ extern "C" int smvp_csr_spmm_describe(const smvp_csr_t *h, int k, char *kernel_n
     return SMVP_OK;
 }
 
+extern "C" int smvp_csr_device_arrays(const smvp_csr_t *h, const int **d_row_ptr, const int **d_col_ind, const double **d_val)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_device_arrays: null handle");
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_device_arrays: plain CSR handles only (this one belongs to a TJDS matrix)");
+    if (d_row_ptr)
+        *d_row_ptr = h->d_row_ptr;
+    if (d_col_ind)
+        *d_col_ind = h->d_col_ind;
+    if (d_val)
+        *d_val = h->d_val;
+    return SMVP_OK;
+}
+
+// A^T as a CSR handle of its own: the entries with row and column swapped, in storage order, through the device converter (a
+// stable sort by the new row, then the new column: rows of A^T get ascending columns, ties in h's storage order)
+extern "C" int smvp_csr_create_transposed(smvp_csr_t **out, const smvp_csr_t *h, void *stream)
+{
+    if (out)
+        *out = nullptr;
+    if (!out || !h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_create_transposed: null %s", out ? "handle" : "out");
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_create_transposed: plain CSR handles only (this one belongs to a TJDS matrix)");
+    DeviceScope on(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_create_transposed: allocates and synchronises, so it cannot be captured "
+                                            "(the stream is capturing)");
+    const int t_rows = h->cols, t_cols = h->rows, nnz = h->nnz;
+    int *t_row_ptr = nullptr, *t_col_ind = nullptr;
+    double *t_val = nullptr;
+    smvp_coo_t *coo = nullptr;
+    auto release = [&]() {
+        for (void *p : {(void *)t_row_ptr, (void *)t_col_ind, (void *)t_val, (void *)coo})
+            if (p)
+                (void)hipFree(p);
+    };
+    if (hipMalloc((void **)&t_row_ptr, sizeof(int) * ((size_t)t_rows + 4)) != hipSuccess ||
+        hipMalloc((void **)&t_col_ind, sizeof(int) * std::max<size_t>((size_t)nnz, 4)) != hipSuccess ||
+        hipMalloc((void **)&t_val, sizeof(double) * std::max<size_t>((size_t)nnz, 4)) != hipSuccess ||
+        hipMalloc((void **)&coo, sizeof(smvp_coo_t) * std::max<size_t>((size_t)nnz, 4)) != hipSuccess) {
+        (void)hipGetLastError();
+        release();
+        return smvp::fail(SMVP_ERR_ALLOC, "smvp_csr_create_transposed: cannot allocate the transposed arrays and the entry list (%d entries)", nnz);
+    }
+    int rc = SMVP_OK;
+    const hipError_t e = smvp::launch_csr_swapped_coo(h->d_row_ptr, h->d_col_ind, h->d_val, h->rows, nnz, coo, st);
+    if (e != hipSuccess)
+        rc = smvp::fail(SMVP_ERR_HIP, "smvp_csr_create_transposed: launch failed: %s", hipGetErrorString(e));
+    if (rc == SMVP_OK) {
+        rc = smvp_csr_from_coo_device(coo, t_rows, t_cols, nnz, t_row_ptr, t_col_ind, t_val, stream);  // returns after the work on `stream`
+        if (rc == SMVP_ERR_HIP && strstr(smvp_last_error(), "out of memory")) {
+            (void)hipGetLastError();
+            rc = smvp::fail(SMVP_ERR_ALLOC, "smvp_csr_create_transposed: cannot allocate the sort's buffers (%d entries)", nnz);
+        }
+    }
+    if (rc != SMVP_OK)
+        (void)hipStreamSynchronize(st);  // (nothing of this call may still read the entry list)
+    (void)hipFree(coo);
+    coo = nullptr;
+    smvp_csr_t *t = nullptr;
+    if (rc == SMVP_OK)
+        rc = csr_create_impl(&t, h->device, t_rows, t_cols, nnz, t_row_ptr, t_col_ind, t_val, SMVP_MEM_DEVICE, nullptr, smvp::kFlavorCsr);
+    if (rc != SMVP_OK) {
+        release();
+        return rc;
+    }
+    t->own_row_ptr = t->own_col_ind = t->own_val = true;  // (adopted from this call: the handle frees them)
+    *out = t;
+    return SMVP_OK;
+}
+
 extern "C" void smvp_csr_destroy(smvp_csr_t *h)
 {
     if (!h)
@@ -1543,6 +1619,38 @@ extern "C" int smvp_tjds_describe(const smvp_tjds_t *h, char *kernel_name, size_
     }
     if (alg_bytes)
         *alg_bytes = 12.0 * h->planned_nnz + 4.0 * (h->num_diag + 1.0) + 8.0 * h->cols + 8.0 * h->rows;
+    return SMVP_OK;
+}
+
+// K8: y = A^T x from the handle's own arrays (the true start_pos, not the ref-quirks edit of the plan) and the caller's x.  No plan,
+// no x_perm, nothing of the forward product's state is read or written; every argument is checked before anything is enqueued.
+extern "C" int smvp_tjds_spmv_transposed(smvp_tjds_t *h, const double *d_x, double *d_y, void *stream)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv_transposed: null handle");
+    if ((h->nnz > 0 && !d_x) || (h->cols > 0 && !d_y))
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv_transposed: null %s", h->cols > 0 && !d_y ? "d_y" : "d_x");
+    // the byte ranges the operands span: x[0 .. rows), y[0 .. cols)
+    const unsigned __int128 xa = (uintptr_t)d_x, ya = (uintptr_t)d_y;
+    const unsigned __int128 xb = xa + (unsigned __int128)(unsigned)h->rows * 8u, yb = ya + (unsigned __int128)(unsigned)h->cols * 8u;
+    if (d_x && d_y && h->rows > 0 && h->cols > 0 && xa < yb && ya < xb)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv_transposed: the byte ranges of d_x and d_y overlap");
+    DeviceScope on(h->device);
+    const hipError_t e = smvp::launch_tjds_transposed(h->d_start_pos, h->d_row_ind, h->d_val, h->d_perm, d_x, d_y, h->cols,
+                                                      h->num_diag, (hipStream_t)stream);
+    if (e != hipSuccess)
+        return smvp::fail(SMVP_ERR_HIP, "smvp_tjds_spmv_transposed: launch failed: %s", hipGetErrorString(e));
+    return SMVP_OK;
+}
+
+extern "C" int smvp_tjds_transposed_describe(const smvp_tjds_t *h, char *kernel_name, size_t cap, double *alg_bytes)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_transposed_describe: null handle");
+    if (kernel_name && cap)
+        snprintf(kernel_name, cap, "%s", smvp::tjds_transposed_kernel_name());
+    if (alg_bytes)
+        *alg_bytes = 12.0 * h->nnz + 4.0 * (h->num_diag + 1.0) + 4.0 * h->cols + 8.0 * h->rows + 8.0 * h->cols;
     return SMVP_OK;
 }
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "smvp_amd.h"
+
 namespace smvp {
 
 constexpr int kVectorBlock = 256;   // threads per block, csr_vector_rows
@@ -35,6 +37,14 @@ int build_spmm_order(const int *row_ptr, int rows, int longest_row, int *order, 
 hipError_t launch_csr_spmm(const int *row_ptr, const int *col_ind, const double *val, const int *order, const double *X,
                            long long ldx, double *Y, long long ldy, int rows, int k, hipStream_t stream);
 void spmm_kernel_name(int k, char *name, size_t cap);  // the passes' kernel symbols
+
+// K8 (smvp_tjds_transposed.hip): y = A^T x from the TJDS arrays -- lane k sums permuted column k and stores y[perm[k]]
+hipError_t launch_tjds_transposed(const int *start_pos, const int *row_ind, const double *val, const int *perm, const double *x,
+                                  double *y, int cols, int num_diag, hipStream_t stream);
+const char *tjds_transposed_kernel_name();
+// smvp_csr_create_transposed (smvp_convert_device.hip): the entries of a CSR matrix with row and column swapped, storage order
+hipError_t launch_csr_swapped_coo(const int *row_ptr, const int *col_ind, const double *val, int rows, int nnz, smvp_coo_t *coo,
+                                  hipStream_t stream);
 
 hipError_t launch_csr_vector(int lanes_per_row, const int *row_ptr, const int *col_ind, const double *val,
                              const double *x, double *y, int rows, hipStream_t stream);

@@ -118,6 +118,7 @@ EXPORTS = [
     "smvp_device_count", "smvp_device_info", "smvp_csr_plan_info", "smvp_tjds_plan_info",
     "smvp_csr_create", "smvp_csr_create_block", "smvp_csr_far_share", "smvp_csr_set_kernel", "smvp_csr_get_kernel", "smvp_csr_gather_spread", "smvp_csr_spmv",
     "smvp_csr_describe", "smvp_csr_plan_launches", "smvp_csr_destroy", "smvp_csr_spmm", "smvp_csr_spmm_describe",
+    "smvp_csr_create_transposed", "smvp_csr_device_arrays", "smvp_tjds_spmv_transposed", "smvp_tjds_transposed_describe",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -157,6 +158,10 @@ def lib():
         L.smvp_csr_destroy.restype = None
         L.smvp_csr_spmm.argtypes = [vp, ci, vp, C.c_longlong, vp, C.c_longlong, vp]
         L.smvp_csr_spmm_describe.argtypes = [vp, ci, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(PlanInfo)]
+        L.smvp_csr_create_transposed.argtypes = [C.POINTER(vp), vp, vp]
+        L.smvp_csr_device_arrays.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.smvp_tjds_spmv_transposed.argtypes = [vp, vp, vp, vp]
+        L.smvp_tjds_transposed_describe.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_double)]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -473,6 +478,20 @@ def spmm_operands(X, Y, rows, cols):
     return k, X.stride(0), Y.stride(0)
 
 
+def transposed_operands(x, y, rows, cols):
+    """Checks the operands of TjdsMatrix.spmv_transposed: x of `rows` and y of `cols` float64 elements, contiguous tensors.
+    Raises ValueError otherwise.  Checks dtype, size and strides only, so it runs on CPU tensors too."""
+    for name, t, n in (("x", x, rows), ("y", y, cols)):
+        if not hasattr(t, "is_contiguous") or not hasattr(t, "numel"):
+            raise ValueError("%s must be a tensor" % name)
+        if str(t.dtype) != "torch.float64":
+            raise ValueError("%s must be float64, not %s" % (name, t.dtype))
+        if t.numel() != n:
+            raise ValueError("%s has %d elements, the matrix needs %d" % (name, t.numel(), n))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous; its strides are %s" % (name, tuple(t.stride())))
+
+
 class CsrMatrix:
     """Device-resident CSR matrix (smvp_csr_t).  Arrays may be numpy (copied to HBM) or torch CUDA tensors (adopted)."""
 
@@ -553,6 +572,27 @@ class CsrMatrix:
         _check(lib().smvp_csr_spmm_describe(self._h, k, name, 256, C.byref(b), C.byref(i)), "smvp_csr_spmm_describe")
         return name.value.decode(), b.value, {"plan_bytes": i.plan_bytes, "build_ms": i.build_ms}
 
+    @classmethod
+    def _wrap(cls, handle, rows, cols, nnz):
+        """A CsrMatrix over a handle the library made itself (it owns its arrays)."""
+        m = cls.__new__(cls)
+        m.rows, m.cols, m.nnz = rows, cols, nnz
+        m._h, m._keep = handle, None
+        return m
+
+    def transposed(self, stream=None):
+        """A^T as a CsrMatrix of its own (smvp_csr_create_transposed): cols x rows, built on the device, independent of this
+        one.  Returns after the work on `stream` has finished."""
+        h = C.c_void_p()
+        _check(lib().smvp_csr_create_transposed(C.byref(h), self._h, _stream_ptr(stream)), "smvp_csr_create_transposed")
+        return CsrMatrix._wrap(h, self.cols, self.rows, self.nnz)
+
+    def device_arrays(self):
+        """(row_ptr, col_ind, val): the device addresses the handle multiplies from, as ints; valid until close()."""
+        rp, ci, v = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().smvp_csr_device_arrays(self._h, C.byref(rp), C.byref(ci), C.byref(v)), "smvp_csr_device_arrays")
+        return rp.value or 0, ci.value or 0, v.value or 0
+
     def close(self):
         if self._h:
             lib().smvp_csr_destroy(self._h)
@@ -590,6 +630,22 @@ class TjdsMatrix:
 
     def spmv(self, y, stream=None):
         _check(lib().smvp_tjds_spmv(self._h, _dev_ptr(y), _stream_ptr(stream)), "smvp_tjds_spmv")
+
+    def spmv_transposed(self, x, y, stream=None):
+        """y = A^T x from the TJDS arrays themselves (smvp_tjds_spmv_transposed, K8): x of `rows`, y of `cols` float64 CUDA
+        elements.  Asynchronous on `stream`; needs no set_x and leaves the forward product's state alone."""
+        transposed_operands(x, y, self.rows, self.cols)
+        if not (x.is_cuda and y.is_cuda):
+            raise ValueError("x and y must be device tensors")
+        _check(lib().smvp_tjds_spmv_transposed(self._h, _dev_ptr(x), _dev_ptr(y), _stream_ptr(stream)),
+               "smvp_tjds_spmv_transposed")
+
+    def transposed_describe(self):
+        """(kernel symbol, algorithmic bytes) of spmv_transposed."""
+        name = C.create_string_buffer(128)
+        b = C.c_double()
+        _check(lib().smvp_tjds_transposed_describe(self._h, name, 128, C.byref(b)), "smvp_tjds_transposed_describe")
+        return name.value.decode(), b.value
 
     def set_mode(self, mode):
         _check(lib().smvp_tjds_set_mode(self._h, mode), "smvp_tjds_set_mode")
