@@ -253,7 +253,21 @@ int smvp_csr_gather_spread(smvp_csr_t *h, double *spread);
  * diagonal (of the whole matrix: smvp_csr_create_block); measured on first use, then kept; -1 where it could not be. */
 int smvp_csr_far_share(smvp_csr_t *h, double *share);
 /* The timed product, main-cli.c:410-416: d_y[0..rows) = A * d_x[0..cols).  Asynchronous
- * on `stream`; d_y is fully overwritten (no pre-zeroing needed). */
+ * on `stream`; d_y is fully overwritten (no pre-zeroing needed).
+ * Values -- what every kernel family, parameter and plan option is held to (tests/test_gpu_special_values.py), the reference
+ * being the serial loop  acc = 0.0; for j in row_ptr[r] .. row_ptr[r+1]: acc += val[j] * x[col_ind[j]]  with every product
+ * rounded before the add (-ffp-contract=off):
+ *   - An element of x influences exactly the rows that store an entry in its column: a NaN or an Inf in a column no entry
+ *     uses changes no bit of y, wherever the column lies (padding, staged windows and column blocks never multiply it in).
+ *   - Stored zeros are multiplied: a stored 0.0 or -0.0 under an infinite x makes its row NaN.
+ *   - With non-finite products a row is what the serial loop gives: NaN if a product is NaN or the row has products of
+ *     +Inf and of -Inf, else +Inf / -Inf if it has such a product; the other rows are finite and within the rounding
+ *     bound of DESIGN.md, whatever the order a family sums in (as long as no sum of finite products overflows).
+ *   - y never holds -0.0: the sum starts from +0.0, so a row of -0.0 products, an exact cancellation and an empty row are +0.0.
+ *   - Subnormal values, products and sums are kept, not flushed.
+ *   - The sign and payload of a NaN are unspecified.
+ *   - The serial loop's very bits: COLSWEEP without column parts on rows stored with ascending columns, and STREAM on rows of
+ *     up to 32 entries (STREAM_CARRY: where such a row lies inside one tile); see SMVP_CSR_KERNEL_*. */
 int smvp_csr_spmv(smvp_csr_t *h, const double *d_x, double *d_y, void *stream);
 /* Name of the dominant kernel symbol of the current plan and its algorithmic
  * byte count per launch: 12*nnz + 4*(rows+1) + 8*cols + 8*rows. */
@@ -332,7 +346,13 @@ int smvp_tjds_set_x(smvp_tjds_t *h, const double *d_x, void *stream);
  * y[row_ind[j]] += val[j] * x_perm[j - start_pos[d]].  In the default mode (ROW_GATHER) and in TWO_PHASE d_y is
  * overwritten; in ATOMIC mode (and ref-quirks mode) d_y must be zero on entry -- the reference
  * zeroes it outside its timed window, main-cli.c:1008 -- and smvp_tjds_zero_y does that on the
- * same stream (it is a no-op when the mode does not need it, so it is always safe to call). */
+ * same stream (it is a no-op when the mode does not need it, so it is always safe to call).
+ * Values: as stated at smvp_csr_spmv, in every mode and stream form, with and without the value cache -- an element of x
+ * (an element of x_perm, a lane past a diagonal's end, a slot of the run tables) influences exactly the rows that store an
+ * entry in its column; stored zeros are multiplied; a row's class under non-finite products is the serial loop's; y never
+ * holds -0.0; subnormals are kept (by the fp64 hardware atomic add of ATOMIC mode too); the sign and payload of a NaN are
+ * unspecified.  ROW_GATHER and TWO_PHASE give the same bits from run to run; ATOMIC adds in the order the hardware takes
+ * the atomics, so its finite rows are only within the rounding bound -- exact where every order gives the same sum. */
 int smvp_tjds_zero_y(smvp_tjds_t *h, double *d_y, void *stream);
 int smvp_tjds_spmv(smvp_tjds_t *h, double *d_y, void *stream);
 /* How the scatter is carried out.

@@ -21,13 +21,17 @@ def bound(terms):
 def check_y(y, ref, scale, terms, exact=False):
     """y (the kernel's) against ref (the oracle's serial loop).  scale = sum_j |a_rj x_j| per row, terms = products per row
     (scalars broadcast).  Every row finite where ref is (a NaN left in y -- a row never written -- fails), within
-    bound(terms) * scale; rows with scale == 0 (empty) equal ref exactly; rows where ref is not finite equal it."""
+    bound(terms) * scale; rows with scale == 0 (empty) equal ref exactly; rows where ref is not finite equal it.  exact: no NaN
+    and the reference's bits, the sign of a zero included."""
     y, ref = np.asarray(y), np.asarray(ref)
     assert y.shape == ref.shape, "y has shape %s, the reference %s" % (y.shape, ref.shape)
     if exact:
         bad = ~((y == ref) | (np.isnan(y) & np.isnan(ref)))
         assert np.array_equal(y, ref), "%d rows differ from the serial loop's bits; first row %d: %r against %r" % (
             bad.sum(), np.flatnonzero(bad)[0] if bad.any() else -1, y[bad][:1], ref[bad][:1])
+        from transposed import assert_bits           # (its one copy; for np.array_equal -0.0 equals 0.0, and the serial loop never gives -0.0)
+
+        assert_bits(y, ref, "rows that must have the serial loop's bits")
         return
     scale = np.broadcast_to(np.asarray(scale, dtype=np.float64), ref.shape)
     terms = np.broadcast_to(np.asarray(terms, dtype=np.float64), ref.shape)

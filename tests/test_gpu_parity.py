@@ -23,6 +23,7 @@ import oracle_binding as ob
 import smvp_toolkit_amd as sm
 from conftest import REPORTS, SAMPLES
 from parity import SPILL_KINDS, TOL, assert_spill_regime, check_guards, check_y, guarded_y, spill_matrix
+from special_values import check_bits
 from test_oracle_golden import _mask
 
 pytestmark = pytest.mark.gpu
@@ -130,17 +131,20 @@ def test_stream_kernel_is_bitwise_serial_on_short_rows(torch):
     lens = np.diff(row_ptr)
     y = gpu_csr(torch, m, n, row_ptr, col_ind, val, x, sm.CSR_KERNEL_STREAM, 256)
     assert np.array_equal(y[lens <= 32], ref[lens <= 32])
+    check_bits(y[lens <= 32], ref[lens <= 32], "the serial loop's bits")
     for tile in (1024, 2048):
         # owner form: wherever the row lies, also across a tile edge
         y = gpu_csr(torch, m, n, row_ptr, col_ind, val, x, sm.CSR_KERNEL_STREAM, tile)
         short = lens <= 32
         assert short.mean() > 0.98
         assert np.array_equal(y[short], ref[short])
+        check_bits(y[short], ref[short], "the serial loop's bits")
         # carry form: rows that fit one tile
         y = gpu_csr(torch, m, n, row_ptr, col_ind, val, x, sm.CSR_KERNEL_STREAM_CARRY, tile)
         one_tile = short & (row_ptr[:-1] // tile == (np.maximum(row_ptr[1:], 1) - 1) // tile)
         assert one_tile.mean() > 0.9
         assert np.array_equal(y[one_tile], ref[one_tile])
+        check_bits(y[one_tile], ref[one_tile], "the serial loop's bits")
 
 
 def test_csr_16_bit_column_offsets(torch):
@@ -170,6 +174,7 @@ def test_csr_16_bit_column_offsets(torch):
             A.spmv(dx, dy)
             torch.cuda.synchronize()
             assert np.array_equal(dy.cpu().numpy(), ref)
+            check_bits(dy.cpu().numpy(), ref, "the serial loop's bits")
         A.set_kernel(sm.CSR_KERNEL_STREAM, 256)                     # 256-entry tiles always read col_ind
         assert A.describe()[0] == "csr_stream_owner<1, 0, false>"
         A.close()
@@ -262,11 +267,13 @@ def test_colsweep_on_scattered_columns(torch):
     A.spmv(dx, dy)
     torch.cuda.synchronize()
     assert np.array_equal(dy.cpu().numpy(), ref)
+    check_bits(dy.cpu().numpy(), ref, "the serial loop's bits")
     A.set_kernel(sm.CSR_KERNEL_STREAM, 0)
     dy.fill_(float("nan"))
     A.spmv(dx, dy)
     torch.cuda.synchronize()
     assert np.array_equal(dy.cpu().numpy(), ref)                  # 32 entries per row: the tile kernel is serial too
+    check_bits(dy.cpu().numpy(), ref, "the serial loop's bits")
     # (round 6: strips of up to 5120 rows -- four of them fill a CU's 160 KB of LDS; 13 bits of the row word, turns capped at 7)
     for rb, want in ((0, 2736), (8192, 8192), (2048, 2048), (4096, 4096), (1024, 1024), (3000, 3000), (1028, 1028), (256, 256),
                      (9768, 9768), (20480, 20480)):
@@ -277,6 +284,7 @@ def test_colsweep_on_scattered_columns(torch):
             A.spmv(dx, dy)
             torch.cuda.synchronize()
             assert np.array_equal(dy.cpu().numpy(), ref)
+            check_bits(dy.cpu().numpy(), ref, "the serial loop's bits")
     # column parts (round 6, never AUTO): the workgroup's wavefronts share two strips / one strip, each taking a half / quarter of the
     # columns into partial sums of its own; a row's sum is its partial sums added part by part -- the same from run to run and
     # inside the rounding bound, not the serial loop's bits
@@ -310,6 +318,7 @@ def test_colsweep_on_scattered_columns(torch):
     A.spmv(dx, dy)
     torch.cuda.synchronize()
     assert np.array_equal(dy.cpu().numpy(), ref)
+    check_bits(dy.cpu().numpy(), ref, "the serial loop's bits")
     A.close()
     # through the reference-shaped entry point too
     coo = sm.make_coo(np.repeat(np.arange(2000), 32), col_ind[:64000] % 2000, val[:64000])
@@ -333,6 +342,7 @@ def test_colsweep_rows_that_meet_in_a_chunk(torch):
     for rb in (0, 1024, 8192, 20480):                    # (20480: strips of 5120 rows, the turns capped at 7 since round 6)
         y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_COLSWEEP, rb)
         assert np.array_equal(y, ref)
+        check_bits(y, ref, "the serial loop's bits")
     # column parts: every part's chunks take their own turns; the sums are the serial ones up to the association part by part
     scale = row_scale(row_ptr, col_ind, val, x)
     for rb, parts in ((1024, 2), (1024, 4), (5120, 4), (1024, 8), (256, 8)):
@@ -425,6 +435,7 @@ def test_binned_plan_on_the_random_model(torch, near):
     short = np.diff(row_ptr) <= 16               # (the window plan sums a longer row across a wavefront)
     assert 0.3 < far.mean() < 0.5 and (short & ~has_far).sum() > 1000
     assert np.array_equal(ys[0][short & ~has_far], ref[short & ~has_far])
+    check_bits(ys[0][short & ~has_far], ref[short & ~has_far], "the serial loop's bits")
     info = A.plan_info()
     n, nf = len(val), int(far.sum())
     assert info["matrix_bytes"] == 12.0 * n + 4.0 * (rows + 1)
@@ -2173,6 +2184,7 @@ def test_fuzz_all_kernels_against_oracle(torch, seed):
     lens = np.diff(row_ptr)
     y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_STREAM, 0)
     assert np.array_equal(y[lens <= 32], ref[lens <= 32])          # short rows: the serial loop's bits
+    check_bits(y[lens <= 32], ref[lens <= 32], "the serial loop's bits")
     coo = sm.make_coo(np.repeat(np.arange(rows), lens), col_ind, val)
     coo = coo[np.random.default_rng(seed).permutation(len(coo))]
     for mode in TJDS_MODES:
@@ -2309,6 +2321,7 @@ def test_config4_full_size_properties(torch):
     k = 20_000
     ref = ob.csr_spmv(row_ptr[:k + 1].copy(), col_ind[:row_ptr[k]], val[:row_ptr[k]], xa.cpu().numpy())
     assert np.array_equal(ya.cpu().numpy()[:k], ref)        # ascending column order inside every row: the serial bits
+    check_bits(ya.cpu().numpy()[:k], ref, "the serial loop's bits")
     # ... on all 10 M rows: the last generation of workgroups and the entries past 2^31 bytes of val against the oracle
     check_y(ya.cpu().numpy(), ob.csr_spmv(row_ptr, col_ind, val, xa.cpu().numpy()), 0, 32, exact=True)
     for kernel in (sm.CSR_KERNEL_STREAM, sm.CSR_KERNEL_STREAM_CARRY):
