@@ -402,6 +402,32 @@ int smvp_tjds_spmv_transposed(smvp_tjds_t *h, const double *d_x, double *d_y, vo
 /* Its kernel symbol and algorithmic bytes 12 nnz + 4 (D + 1) + 4 cols + 8 rows + 8 cols (SURVEY 8(d)'s TJDS figure with x and y
  * changing places, plus perm, which this product reads once where the forward one reads the permuted operand). */
 int smvp_tjds_transposed_describe(const smvp_tjds_t *h, char *kernel_name, size_t cap, double *alg_bytes);
+/* The block form of route 2, kernel K9: d_Y[c*ldy + v] = (A^T X)(c, v) for c < cols, v < k, from the handle's own val / row_ind /
+ * start_pos / perm.  For an M x N matrix X is M x k and Y is N x k, both row-major doubles with leading dimensions ldx >= k,
+ * ldy >= k: the operand conventions of smvp_csr_spmm with the rows and columns of A changing places (a contiguous (n, k) array,
+ * or a slice of columns of a wider one; column-major operands are not supported).
+ *   - Bits: every Y(c, v) is bit for bit the transposed-product definition above smvp_csr_create_transposed applied to column v
+ *     of X -- acc = 0.0; for the stored entries of column c in ascending row, ties in TJDS storage order: acc += val * X(r, v),
+ *     each product rounded before the add (-ffp-contract=off) -- for every column length, k, ldx and ldy, on every stream, the
+ *     same on every run.  For k = 1, ldx = ldy = 1 these are the bits of smvp_tjds_spmv_transposed.
+ *   - Writes: Y(c, v) for v < k is overwritten (no pre-zeroing); a column without entries gets +0.0; Y(c, v) for k <= v < ldy is
+ *     never touched; Y never holds -0.0.
+ *   - Values: as stated at smvp_csr_spmv -- an element of X influences exactly the outputs whose column stores an entry in its
+ *     row (a lane whose column has ended leaves its product out with a select and never multiplies by 0); stored zeros are
+ *     multiplied; subnormals are kept.
+ *   - State: no plan and no second copy.  The call reads nothing of smvp_tjds_set_x, the modes' plans, the value cache or the
+ *     ref-quirks edit, so its result does not depend on them; it is capturable into a hipGraph from the first call on a fresh
+ *     handle; a forward smvp_tjds_spmv after it gives the bits it gave before, without a new smvp_tjds_set_x.
+ *   - The matrix is read once per 16 vectors: ceil(k / 16) passes.
+ *   - SMVP_ERR_INVALID, before anything is enqueued, for: a NULL handle; k < 1, ldx < k or ldy < k; a NULL d_X with nnz > 0 or
+ *     a NULL d_Y with cols > 0; byte ranges of X ((rows - 1) ldx + k doubles) and Y ((cols - 1) ldy + k doubles) that overlap.
+ *   - Asynchronous on `stream`. */
+int smvp_tjds_spmm_transposed(smvp_tjds_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream);
+/* The kernel symbols of a product with k vectors (one per pass, joined by " + ") and its algorithmic bytes
+ * 12 nnz + 4 (D + 1) + 4 cols + 8 k (rows + cols): smvp_tjds_transposed_describe's figure with k operands, whatever the number
+ * of passes.  (The leading dimensions are not known here: for k = 1 the symbol is the one-lane pass's; a call with k = 1 and
+ * ldx = ldy = 1 runs smvp_tjds_spmv_transposed's kernel, which gives the same bits.) */
+int smvp_tjds_spmm_transposed_describe(const smvp_tjds_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes);
 void smvp_tjds_destroy(smvp_tjds_t *h);
 
 /* ------------------------------------------- several GPUs, one host process */

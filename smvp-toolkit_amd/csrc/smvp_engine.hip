@@ -1654,6 +1654,44 @@ extern "C" int smvp_tjds_transposed_describe(const smvp_tjds_t *h, char *kernel_
     return SMVP_OK;
 }
 
+// K9: Y = A^T X for k vectors from the handle's own arrays and the caller's X, as K8 for one: no plan, nothing of the forward
+// product's state is read or written; every argument is checked before anything is enqueued.
+extern "C" int smvp_tjds_spmm_transposed(smvp_tjds_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: null handle");
+    if (k < 1 || ldx < k || ldy < k)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: k = %d, ldx = %lld, ldy = %lld (need k >= 1, ldx >= k, ldy >= k)", k,
+                          ldx, ldy);
+    if ((h->nnz > 0 && !d_X) || (h->cols > 0 && !d_Y))
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: null %s", h->cols > 0 && !d_Y ? "d_Y" : "d_X");
+    // the byte ranges the operands span: X(r, v) for r < rows, Y(c, v) for c < cols (v < k)
+    const unsigned __int128 xa = (uintptr_t)d_X, ya = (uintptr_t)d_Y;
+    const unsigned __int128 xb = xa + ((unsigned __int128)(h->rows > 0 ? h->rows - 1 : 0) * (unsigned long long)ldx + (unsigned)k) * 8u;
+    const unsigned __int128 yb = ya + ((unsigned __int128)(h->cols > 0 ? h->cols - 1 : 0) * (unsigned long long)ldy + (unsigned)k) * 8u;
+    if (d_X && d_Y && h->rows > 0 && h->cols > 0 && xa < yb && ya < xb)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: the byte ranges of d_X and d_Y overlap");
+    DeviceScope on(h->device);
+    const hipError_t e = smvp::launch_tjds_spmm_transposed(h->d_start_pos, h->d_row_ind, h->d_val, h->d_perm, d_X, ldx, d_Y, ldy,
+                                                           h->cols, h->num_diag, k, (hipStream_t)stream);
+    if (e != hipSuccess)
+        return smvp::fail(SMVP_ERR_HIP, "smvp_tjds_spmm_transposed: launch failed: %s", hipGetErrorString(e));
+    return SMVP_OK;
+}
+
+extern "C" int smvp_tjds_spmm_transposed_describe(const smvp_tjds_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed_describe: null handle");
+    if (k < 1)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed_describe: k = %d (need k >= 1)", k);
+    if (kernel_name && cap)
+        smvp::tjds_spmm_transposed_kernel_name(k, kernel_name, cap);
+    if (alg_bytes)
+        *alg_bytes = 12.0 * h->nnz + 4.0 * (h->num_diag + 1.0) + 4.0 * h->cols + 8.0 * k * ((double)h->rows + h->cols);
+    return SMVP_OK;
+}
+
 // Which values the one-kernel product keeps a second copy of: those of val lines whose 16 entries belong to
 // `min_tiles` tiles or more (0: none -- every value is read from val itself).  Rebuilds the plan.
 extern "C" int smvp_tjds_set_value_cache(smvp_tjds_t *h, int min_tiles)

@@ -42,6 +42,11 @@ void spmm_kernel_name(int k, char *name, size_t cap);  // the passes' kernel sym
 hipError_t launch_tjds_transposed(const int *start_pos, const int *row_ind, const double *val, const int *perm, const double *x,
                                   double *y, int cols, int num_diag, hipStream_t stream);
 const char *tjds_transposed_kernel_name();
+// K9 (smvp_tjds_spmm_transposed.hip): Y = A^T X for k vectors -- a group of G lanes sums permuted column c for G vectors and
+// stores Y(perm[c], v); kSpmmMaxVectors vectors per pass
+hipError_t launch_tjds_spmm_transposed(const int *start_pos, const int *row_ind, const double *val, const int *perm, const double *X,
+                                       long long ldx, double *Y, long long ldy, int cols, int num_diag, int k, hipStream_t stream);
+void tjds_spmm_transposed_kernel_name(int k, char *name, size_t cap);  // the passes' kernel symbols
 // smvp_csr_create_transposed (smvp_convert_device.hip): the entries of a CSR matrix with row and column swapped, storage order
 hipError_t launch_csr_swapped_coo(const int *row_ptr, const int *col_ind, const double *val, int rows, int nnz, smvp_coo_t *coo,
                                   hipStream_t stream);

@@ -119,6 +119,7 @@ EXPORTS = [
     "smvp_csr_create", "smvp_csr_create_block", "smvp_csr_far_share", "smvp_csr_set_kernel", "smvp_csr_get_kernel", "smvp_csr_gather_spread", "smvp_csr_spmv",
     "smvp_csr_describe", "smvp_csr_plan_launches", "smvp_csr_destroy", "smvp_csr_spmm", "smvp_csr_spmm_describe",
     "smvp_csr_create_transposed", "smvp_csr_device_arrays", "smvp_tjds_spmv_transposed", "smvp_tjds_transposed_describe",
+    "smvp_tjds_spmm_transposed", "smvp_tjds_spmm_transposed_describe",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -162,6 +163,8 @@ def lib():
         L.smvp_csr_device_arrays.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.smvp_tjds_spmv_transposed.argtypes = [vp, vp, vp, vp]
         L.smvp_tjds_transposed_describe.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_double)]
+        L.smvp_tjds_spmm_transposed.argtypes = [vp, ci, vp, C.c_longlong, vp, C.c_longlong, vp]
+        L.smvp_tjds_spmm_transposed_describe.argtypes = [vp, ci, C.c_char_p, C.c_size_t, C.POINTER(C.c_double)]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -645,6 +648,23 @@ class TjdsMatrix:
         name = C.create_string_buffer(128)
         b = C.c_double()
         _check(lib().smvp_tjds_transposed_describe(self._h, name, 128, C.byref(b)), "smvp_tjds_transposed_describe")
+        return name.value.decode(), b.value
+
+    def spmm_transposed(self, X, Y, stream=None):
+        """Y = A^T X for k vectors at once from the TJDS arrays themselves (smvp_tjds_spmm_transposed, K9): X (rows x k) and
+        Y (cols x k) are float64 CUDA tensors with stride(1) == 1, ldx = X.stride(0), ldy = Y.stride(0).  Every column of Y is
+        the transposed product's bits.  Asynchronous on `stream`; needs no set_x and no plan."""
+        k, ldx, ldy = spmm_operands(X, Y, self.cols, self.rows)
+        if not (X.is_cuda and Y.is_cuda):
+            raise ValueError("X and Y must be device tensors")
+        _check(lib().smvp_tjds_spmm_transposed(self._h, k, _dev_ptr(X), ldx, _dev_ptr(Y), ldy, _stream_ptr(stream)),
+               "smvp_tjds_spmm_transposed")
+
+    def spmm_transposed_describe(self, k):
+        """(kernel symbols, algorithmic bytes for k vectors) of spmm_transposed."""
+        name = C.create_string_buffer(256)
+        b = C.c_double()
+        _check(lib().smvp_tjds_spmm_transposed_describe(self._h, k, name, 256, C.byref(b)), "smvp_tjds_spmm_transposed_describe")
         return name.value.decode(), b.value
 
     def set_mode(self, mode):
