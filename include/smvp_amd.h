@@ -172,7 +172,19 @@ int smvp_device_info(int device, char *name, size_t name_cap, int *compute_units
  * second time, copied when the plan is built: a handle over adopted device arrays (SMVP_MEM_DEVICE) whose
  * val / col_ind are then changed in place must be re-planned (smvp_csr_set_kernel) or re-created.  (smvp_csr_spmm keeps no
  * second copy: its plan depends on row_ptr alone, and it reads val / col_ind themselves.)  A handle made by
- * smvp_csr_create_transposed is a second copy of all the entries: after such a change it is stale and must be created again. */
+ * smvp_csr_create_transposed is a second copy of all the entries: after such a change it is stale and must be created again.
+ * Family by family, for val changed in place (tests/test_gpu_adopted.py holds every sentence):
+ *   VECTOR, STREAM, STREAM_CARRY   read val itself: the next smvp_csr_spmv multiplies the new values, without any call (STREAM's
+ *                                  second copy is of columns only);
+ *   COLSWEEP, BINNED               keep a copy of the values: call smvp_csr_set_kernel (the same kernel and param will do) first;
+ *   AUTO                           is one of the above: call smvp_csr_set_kernel(h, SMVP_CSR_KERNEL_AUTO, 0) unless
+ *                                  smvp_csr_get_kernel names a family of the first line.
+ * After col_ind changed in place call smvp_csr_set_kernel on every family (smvp_csr_spmm alone needs no call): the plan, its
+ * describe() and its plan bytes are then those of a new handle over the same arrays, and AUTO chooses for the columns that are
+ * there now (the gather spread and the far share are measured again).  A re-plan does not check the indices again: the caller
+ * keeps changed columns inside [0, cols).  row_ptr may not be changed.  The arrays themselves are only ever read: every plan
+ * builder, the ones that sort included, leaves them bit for bit as they were, smvp_csr_destroy frees none of them, and
+ * several handles may share them. */
 enum {
     SMVP_CSR_KERNEL_AUTO = 0,
     SMVP_CSR_KERNEL_VECTOR = 1,      /* one (sub-)wavefront per row, __shfl_down sums */
@@ -231,7 +243,9 @@ typedef struct smvp_tjds smvp_tjds_t; /* device-resident TJDS matrix + launch pl
  * live in HBM, laid out exactly as CSRData (main-cli.c:61-66).  At most 2^31 - 1 - 65536 =
  * 2 147 418 111 entries (smvp_tjds_create too): more is SMVP_ERR_UNSUPPORTED.  row_ptr is
  * always read from the host copy as well to build the launch plan, so with
- * SMVP_MEM_DEVICE pass the host row_ptr in `host_row_ptr` (NULL = copy it back). */
+ * SMVP_MEM_DEVICE pass the host row_ptr in `host_row_ptr` (NULL = copy it back).
+ * Adopted col_ind and val (SMVP_MEM_DEVICE) must be 16-byte aligned -- the tile kernels read them four and two at a time --
+ * or the call is refused with SMVP_ERR_INVALID and *out is left alone; row_ptr needs no more than an int's alignment. */
 int smvp_csr_create(smvp_csr_t **out, int device, int rows, int cols, int nnz,
                     const int *row_ptr, const int *col_ind, const double *val,
                     int mem_kind, const int *host_row_ptr);
@@ -247,10 +261,11 @@ int smvp_csr_set_kernel(smvp_csr_t *h, int kernel, int param); /* param: lanes p
 int smvp_csr_get_kernel(const smvp_csr_t *h, int *kernel, int *param);
 /* What AUTO's choice of COLSWEEP rests on: the share (0 ... 1) of the matrix's gathers that pull their own
  * 128-byte line of x through the L2, estimated on 64 samples of 65536 consecutive entries of col_ind (measured
- * on first use, then kept); -1 for matrices of fewer than 4 M entries, which are not sampled. */
+ * on first use, kept until the next smvp_csr_set_kernel); -1 for matrices of fewer than 4 M entries, which are not sampled. */
 int smvp_csr_gather_spread(smvp_csr_t *h, double *spread);
 /* What AUTO's choice of BINNED rests on besides the spread: the share (0 ... 1) of the entries further than 4096 from the
- * diagonal (of the whole matrix: smvp_csr_create_block); measured on first use, then kept; -1 where it could not be. */
+ * diagonal (of the whole matrix: smvp_csr_create_block); measured on first use, kept until the next smvp_csr_set_kernel; -1 where
+ * it could not be. */
 int smvp_csr_far_share(smvp_csr_t *h, double *share);
 /* The timed product, main-cli.c:410-416: d_y[0..rows) = A * d_x[0..cols).  Asynchronous
  * on `stream`; d_y is fully overwritten (no pre-zeroing needed).
@@ -335,7 +350,9 @@ int smvp_csr_device_arrays(const smvp_csr_t *h, const int **d_row_ptr, const int
 void smvp_csr_destroy(smvp_csr_t *h);
 
 /* Device-side half of smvp_tjds_compute (main-cli.c:756-763,944-967): val,
- * row_ind, start_pos as TJDSData (main-cli.c:70-75) plus perm. */
+ * row_ind, start_pos as TJDSData (main-cli.c:70-75) plus perm.  Adopted arrays (SMVP_MEM_DEVICE) need no alignment beyond
+ * their element's own (8 bytes for val, 4 for the others): unlike smvp_csr_create there is no 16-byte rule and no refusal,
+ * in any mode and in the transposed products -- every kernel reads them one element at a time. */
 int smvp_tjds_create(smvp_tjds_t **out, int device, int rows, int cols, int nnz, int num_diag,
                      const int *perm, const int *start_pos, const int *row_ind,
                      const double *val, int mem_kind);
@@ -352,7 +369,10 @@ int smvp_tjds_set_x(smvp_tjds_t *h, const double *d_x, void *stream);
  * entry in its column; stored zeros are multiplied; a row's class under non-finite products is the serial loop's; y never
  * holds -0.0; subnormals are kept (by the fp64 hardware atomic add of ATOMIC mode too); the sign and payload of a NaN are
  * unspecified.  ROW_GATHER and TWO_PHASE give the same bits from run to run; ATOMIC adds in the order the hardware takes
- * the atomics, so its finite rows are only within the rounding bound -- exact where every order gives the same sum. */
+ * the atomics, so its finite rows are only within the rounding bound -- exact where every order gives the same sum.
+ * Adopted arrays (SMVP_MEM_DEVICE) whose val is changed in place: ATOMIC and TWO_PHASE read val itself, so the next
+ * smvp_tjds_spmv multiplies the new values without any call; ROW_GATHER keeps copies (the value cache, and with or without it
+ * the values a tile reads past its end) and needs smvp_tjds_set_value_cache or re-creation first, see there. */
 int smvp_tjds_zero_y(smvp_tjds_t *h, double *d_y, void *stream);
 int smvp_tjds_spmv(smvp_tjds_t *h, double *d_y, void *stream);
 /* How the scatter is carried out.
@@ -380,7 +400,9 @@ int smvp_tjds_set_tile(smvp_tjds_t *h, int entries_per_tile); /* ROW_GATHER: 256
  * different tiles (default 2: every line that is not one tile's alone -- 56 % of the values of memplus x944, 21 % of pwt
  * x459; 4 until round 4), stored tile by tile and read coalesced; all other values are read from val itself.
  * 0 = no cache (every value from val).  The sums and their order do not depend on it.  A handle over adopted device
- * arrays (SMVP_MEM_DEVICE) must be re-created, or this called again, after val has been changed in place. */
+ * arrays (SMVP_MEM_DEVICE) must be re-created, or this called again, after val has been changed in place: with the same
+ * min_tiles is enough, and with 0 it is needed as well (the values a tile reads past its end are a copy with or without the
+ * cache). */
 int smvp_tjds_set_value_cache(smvp_tjds_t *h, int min_tiles);
 int smvp_tjds_get_value_cache(const smvp_tjds_t *h, int *min_tiles, long long *cached_entries);
 /* Reference-defect emulation for parity with the committed TJDS reports
@@ -391,7 +413,8 @@ int smvp_tjds_describe(const smvp_tjds_t *h, char *kernel_name, size_t cap, doub
 int smvp_tjds_plan_info(const smvp_tjds_t *h, smvp_plan_info_t *out); /* plan: x_perm, the work items, the selected modes' plans */
 /* Route 2 of the transposed product (definition above smvp_csr_create_transposed), kernel K8: d_y[0..cols) = A^T * d_x[0..rows)
  * from the handle's own val / row_ind / start_pos / perm -- TJDS stores A by columns, so permuted column k is a row of A^T and
- * one lane sums it from top to bottom.  No second copy, no plan, no atomics; asynchronous on `stream` and capturable into a
+ * one lane sums it from top to bottom.  No second copy (val of adopted arrays changed in place is seen by the next call, and
+ * by smvp_tjds_spmm_transposed's), no plan, no atomics; asynchronous on `stream` and capturable into a
  * hipGraph from the first call.  Every y[c] is the definition's bits for every column length, the same on every run.  It reads
  * neither the permuted operand of smvp_tjds_set_x nor any mode's plan: the result does not depend on smvp_tjds_set_mode /
  * set_tile / set_value_cache / set_ref_quirks, and a forward smvp_tjds_spmv after it gives the bits it gave before it without

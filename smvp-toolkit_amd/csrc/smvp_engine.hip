@@ -838,6 +838,9 @@ extern "C" int smvp_csr_set_kernel(smvp_csr_t *h, int kernel, int param)
         (param < 2 || param > 64 || (param & (param - 1)) != 0))
         return smvp::fail(SMVP_ERR_INVALID, "lanes per row must be a power of two in [2, 64]");
     DeviceScope on(h->device);
+    // the documented re-plan after col_ind of adopted arrays changed in place: what AUTO measured belongs to the columns that
+    // were there, so both figures are forgotten and taken again by whoever asks next (AUTO below, or the two getters)
+    h->spread = h->far_share = -2.0;
     if (!choose_csr_kernel(h, kernel, param))
         return smvp::fail(SMVP_ERR_INVALID, "entries per tile must be 256 (stream only), 1024 or 2048 for the kernel "
                                             "this matrix resolves to (column sweep: 256 ... 20480 rows per block, a multiple of 4; binned: the near band, >= 0)");
