@@ -1,13 +1,9 @@
-// smvp_engine.hip -- device-resident matrices, launch plans and the two
-// reference-shaped compute entry points.
+// smvp_engine.hip -- device-resident matrices and their launch plans.
 //
-//   smvp_csr_compute   replaces main-cli.c:325-469
-//   smvp_tjds_compute  replaces main-cli.c:734-1162
-// The conversion halves live in smvp_convert.cpp (host); this file owns what
-// the reference keeps in CSRData / TJDSData (main-cli.c:61-75) once it is in
-// HBM, the per-matrix launch plan, and the timed iteration loop
-// (main-cli.c:402-420, :1004-1024) with hipEvents in place of clock_gettime.
-#include "smvp_common.h"
+// This file owns what the reference keeps in CSRData / TJDSData (main-cli.c:61-75) once it is in HBM, and the per-matrix
+// launch plans.  The conversion halves live in smvp_convert.cpp (host); the timed iteration loop and the two
+// reference-shaped compute entry points live in smvp_run.hip, which sees the handles through smvp_engine.h only.
+#include "smvp_engine.h"
 #include "smvp_kernels.h"
 
 #include <algorithm>
@@ -17,34 +13,11 @@
 #include <string>
 #include <vector>
 
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return smvp::fail(SMVP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-namespace {
-
-// Runs the launches of one call on the handle's device, whatever the caller's current device is.
-struct DeviceScope {
-    int prev = -1;
-    bool switched = false;
-    explicit DeviceScope(int device)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != device)
-            switched = hipSetDevice(device) == hipSuccess;
-    }
-    ~DeviceScope()
-    {
-        if (switched)
-            (void)hipSetDevice(prev);
-    }
-};
-
+using smvp::DeviceScope;
 using smvp::kMaxEntries;
+using smvp::usable_device;
 
-int usable_device(int device)
+int smvp::usable_device(int device)
 {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
@@ -54,19 +27,57 @@ int usable_device(int device)
     return SMVP_OK;
 }
 
-template <class T>
-int to_device(T **dst, const T *src, size_t count, int mem_kind, bool *owned)
+namespace {
+
+double wall_ms()
 {
-    if (mem_kind == SMVP_MEM_DEVICE) {
-        *dst = const_cast<T *>(src);
-        *owned = false;
-        return SMVP_OK;
-    }
-    *owned = true;
+    timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
+}
+
+// `count` elements of host memory as a device array of its own (never shorter than four elements)
+template <class T>
+int upload(T **dst, const T *src, size_t count)
+{
     HIP_TRY(hipMalloc((void **)dst, std::max<size_t>(count, 4) * sizeof(T)));
     if (count)
         HIP_TRY(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
     return SMVP_OK;
+}
+
+template <class T>
+int upload(T **dst, const std::vector<T> &src) { return upload(dst, src.data(), src.size()); }
+
+// a caller's array: adopted where it is on the device already, else uploaded
+template <class T>
+int to_device(T **dst, const T *src, size_t count, int mem_kind, bool *owned)
+{
+    *owned = mem_kind != SMVP_MEM_DEVICE;
+    if (*owned)
+        return upload(dst, src, count);
+    *dst = const_cast<T *>(src);
+    return SMVP_OK;
+}
+
+// The call allocates or synchronises: refused with `why` while `st` is capturing.
+int refuse_capture(hipStream_t st, const char *why)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return smvp::fail(SMVP_ERR_INVALID, "%s", why);
+    return SMVP_OK;
+}
+
+// Do the byte ranges of two operands meet?  An operand is n rows of k doubles, ld doubles from one row to the next (a vector:
+// ld = 1, k = 1); without rows it has no bytes.
+bool operands_overlap(const double *a, long long lda, int na, const double *b, long long ldb, int nb, int k)
+{
+    const unsigned __int128 a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    const unsigned __int128 a1 = a0 + (na > 0 ? ((unsigned __int128)(na - 1) * (unsigned long long)lda + (unsigned)k) * 8u : 0);
+    const unsigned __int128 b1 = b0 + (nb > 0 ? ((unsigned __int128)(nb - 1) * (unsigned long long)ldb + (unsigned)k) * 8u : 0);
+    return a && b && na > 0 && nb > 0 && a0 < b1 && b0 < a1;
 }
 
 // Device-resident index arrays are range-checked on the device (host arrays are checked on the host).
@@ -89,20 +100,88 @@ int check_device_indices(const int *d_a, long long n, int limit, const char *wha
     return SMVP_OK;
 }
 
-template <class T>
-int upload(T **dst, const std::vector<T> &src)
-{
-    HIP_TRY(hipMalloc((void **)dst, std::max<size_t>(src.size(), 4) * sizeof(T)));
-    if (!src.empty())
-        HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return SMVP_OK;
-}
-
 }  // namespace
 
 // ===========================================================================
 // CSR
 // ===========================================================================
+// what a TJDS flavour borrows from its smvp_tjds owner (set before the tile plan is built)
+struct TjdsSource {
+    const int *pos = nullptr;
+    const int *start_pos = nullptr;
+    int num_diag = 0;
+    // the two-phase product's second phase: `val` holds the products of the first phase (written anew before every launch: no value
+    // cache, overflow entries by position), the operand is the unit vector (no x gather)
+    bool unit_operand = false;
+};
+
+// The launch plans of a CSR handle.  Each is a plain struct with one release function that frees what the struct owns and
+// resets it to its default value (the idiom of smvp::BinnedPlan / free_binned_plan); what a caller asked for and must survive
+// a re-plan -- the tile size, the value cache's threshold -- stays on the handle.
+
+// STREAM / STREAM_CARRY: tiles of 256 * smvp_csr::vpt entries, and the tile-ordered streams of the TJDS flavours; build_tile_plan
+struct TilePlan {
+    int ntiles = 0;
+    int *d_tile_row = nullptr;
+    int *d_tile_next = nullptr;   // STREAM: row_ptr[first row of the next tile]
+    // STREAM, plain CSR, tiles of 1024 / 2048 entries whose columns all span < 65536: col_ind a second time as 16-bit
+    // offsets from the tile's smallest column (10 instead of 12 bytes per entry; csr_stream_owner<., kFlavorCsr16, .>)
+    unsigned short *d_col16 = nullptr;
+    int *d_col_base = nullptr;
+    // STREAM: every row's first entry as a 16-bit offset from the first entry of the tile the row
+    // starts in -- what phase 2 reads instead of row_ptr (2 instead of 4 bytes per row)
+    unsigned short *d_row_rel = nullptr;
+    int *d_carry_row = nullptr;   // STREAM_CARRY
+    double *d_carry = nullptr;    // STREAM_CARRY
+    // TjdsS: per-tile TJDS-ordered streams and the tiles' overflow entries
+    int *d_pos_sorted = nullptr, *d_meta = nullptr, *d_ovf_ptr = nullptr, *d_ovf_k = nullptr;
+    double *d_ovf_val = nullptr;  // TjdsS / H: the overflow entries' values (read coalesced by the tile that finishes the row)
+    // TjdsS: values of the entries whose val lines scatter over cache_min_tiles tiles or more, kept tile by tile (0: none).
+    // A line split over two or three tiles is the edge between neighbouring tiles (they run together on one XCD: an L2
+    // hit); from four on its entries belong to unrelated rows.  Measured on memplus x944 (profiles/r03_tjds_forms_measured.txt):
+    // none 0.555 ms / 3.66 GB moved, >= 8 tiles 0.461 / 2.92 (20 % of the values cached), >= 4 tiles 0.444 / 2.73 (35 %).
+    int *d_cache_ptr = nullptr;
+    double *d_val_cache = nullptr;
+    int cached_total = 0, ovf_total = 0;
+    // TjdsH: the 16-bit second word of every entry, the tiles' runs (start_pos of each run's diagonal), each group of 32's run
+    unsigned short *d_group_run = nullptr;
+    unsigned *d_word32 = nullptr;
+    int *d_run_ptr = nullptr, *d_run_tab = nullptr;
+    int runs_total = 0;
+};
+
+// COLSWEEP: the entries a second time, every strip sorted by column (built on the device); build_sweep_plan
+struct SweepPlan {
+    int rb = 0, per_launch = 0;  // rows per workgroup (four wavefronts), workgroups that start together
+    int parts = 1;               // column parts per strip (1: every row summed in the serial loop's order; 2 / 4 / 8: see sweep_param)
+    int g = 0;                   // chunks in flight per wavefront (fixed when the plan is built)
+    long long *d_ptr = nullptr;
+    int *d_col = nullptr;
+    double *d_val = nullptr;
+    unsigned short *d_row = nullptr;
+    double *d_part = nullptr;    // XCD-private column parts: 8 * rows partial sums
+};
+
+// BINNED: the entries a second time, split by |column - row| > band: the near part as the window plan bin.nw (K6) or,
+// where that does not suit, as CSR arrays of its own run by the tile kernel through the nested handle `near`; the far
+// part as the two streams and the bins of smvp_binned.hip; build_binned
+struct BinnedSide {
+    smvp::BinnedPlan bin;
+    smvp_csr *near = nullptr;
+    // with the window plan: pass A (it needs x only) goes onto a stream of its own, ahead of the near part, and
+    // the near part's workgroups take the CUs as pass A's last ones leave them
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+};
+
+// smvp_csr_spmm (K7, smvp_spmm.hip): the rows ordered by length inside blocks of kSpmmBlockRows, built by the first call
+// and kept whatever the SpMV plan is (it depends on row_ptr only)
+struct SpmmPlan {
+    int *d_order = nullptr;
+    bool planned = false;
+    double build_ms = 0.0;
+};
+
 struct smvp_csr {
     int device = 0;
     int rows = 0, cols = 0, nnz = 0;
@@ -113,105 +192,78 @@ struct smvp_csr {
     double *d_val = nullptr;
     bool own_row_ptr = false, own_col_ind = false, own_val = false;
     std::vector<int> h_row_ptr;  // kept for re-planning
+    int max_row_len = 0;
 
-    // what an entry of the stream is (smvp_kernels.h kFlavor*): plain CSR, the unit-value form (second phase of the
-    // two-phase TJDS product), or a TJDS matrix regrouped by rows (the one-kernel TJDS product); the TJDS flavours
+    // what an entry of the stream is (smvp_kernels.h kFlavor*): plain CSR, or a TJDS matrix regrouped by rows (the one-kernel
+    // TJDS product; as kFlavorTjdsH with unit_operand the second phase of the two-phase product); the TJDS flavours
     // borrow these arrays from their smvp_tjds owner
     int flavor = smvp::kFlavorCsr;
-    const int *d_pos = nullptr;       // TjdsK: what the kernel reads; TjdsS: the row-major stream the tiles are sorted from
-    const int *d_start_pos = nullptr;
-    int num_diag = 0;
-    // TjdsS: per-tile TJDS-ordered streams and the tiles' overflow entries, owned, rebuilt with the tile plan
-    int *d_pos_sorted = nullptr, *d_meta = nullptr, *d_ovf_ptr = nullptr, *d_ovf_k = nullptr;
-    double *d_ovf_val = nullptr;  // TjdsS / H: the overflow entries' values (read coalesced by the tile that finishes the row)
-    // TjdsS: values of the entries whose val lines scatter over cache_min_tiles tiles or more, kept tile by tile (0: none).
-    // A line split over two or three tiles is the edge between neighbouring tiles (they run together on one XCD: an L2
-    // hit); from four on its entries belong to unrelated rows.  Measured on memplus x944 (profiles/r03_tjds_forms_measured.txt):
-    // none 0.555 ms / 3.66 GB moved, >= 8 tiles 0.461 / 2.92 (20 % of the values cached), >= 4 tiles 0.444 / 2.73 (35 %).
-    int cache_min_tiles = 2, cached_total = 0, ovf_total = 0;  // 2: every val line that is not one tile's alone (measured, r04)
-    bool unit_operand = false;  // TjdsH as the second phase of the two-phase TJDS product (see TjdsSource)
-    int *d_cache_ptr = nullptr;
-    double *d_val_cache = nullptr;
-    // TjdsH: the 16-bit second word of every entry, the tiles' runs (start_pos of each run's diagonal), each group of 32's run
-    unsigned short *d_group_run = nullptr;
-    unsigned *d_word32 = nullptr;
-    int *d_run_ptr = nullptr, *d_run_tab = nullptr;
-    int runs_total = 0;
+    TjdsSource src;  // src.pos: what the TjdsK kernel reads; TjdsS / H: the row-major stream the tiles are sorted from
+    int cache_min_tiles = 2;    // TjdsS / H, see TilePlan::d_val_cache; 2: every val line that is not one tile's alone (measured, r04)
+    bool plain_only = false;    // a nested handle: AUTO stays on the tile kernels
+
     int kernel = SMVP_CSR_KERNEL_AUTO;  // resolved: never AUTO once a plan exists
     int lanes_per_row = 64;             // VECTOR
     int vpt = 4;                        // STREAM: entries per thread (tile = 256 * vpt)
-    int ntiles = 0;
-    int max_row_len = 0;
-    int *d_tile_row = nullptr;
-    int *d_tile_next = nullptr;   // STREAM: row_ptr[first row of the next tile]
-    // STREAM, plain CSR, tiles of 1024 / 2048 entries whose columns all span < 65536: col_ind a second time as 16-bit
-    // offsets from the tile's smallest column (10 instead of 12 bytes per entry; csr_stream_owner<., kFlavorCsr16, .>)
-    unsigned short *d_col16 = nullptr;
-    int *d_col_base = nullptr;
-    // STREAM: every row's first entry as a 16-bit offset from the first entry of the tile the row
-    // starts in -- what phase 2 reads instead of row_ptr (2 instead of 4 bytes per row)
-    unsigned short *d_row_rel = nullptr;
-    bool tile_chosen = false;     // the caller named the tile size (smvp_csr_set_kernel param): the plan keeps it
-    int *d_carry_row = nullptr;   // STREAM_CARRY
-    double *d_carry = nullptr;    // STREAM_CARRY
-    // COLSWEEP: the entries a second time, every strip of sweep_rb / 4 rows sorted by column (built on the device);
-    // sweep_rb = rows per workgroup (four wavefronts, one strip each)
-    int sweep_rb = 0, sweep_per_launch = 0;
-    double *d_sweep_part = nullptr;  // COLSWEEP with XCD-private column parts: 8 * rows partial sums
-    int sweep_parts = 1;       // COLSWEEP: column parts per strip (1: every row summed in the serial loop's order; 2 / 4: see sweep_param)
-    double spread = -2.0;  // share of gathers that pull their own line of x (csr_gather_spread); -2: not measured yet
-    long long *d_sweep_ptr = nullptr;
-    int *d_sweep_col = nullptr;
-    double *d_sweep_val = nullptr;
-    unsigned short *d_sweep_row = nullptr;
-    // BINNED: the entries a second time, split by |column - row| > band: the near part as the window plan bin.nw (K6) or,
-    // where that does not suit, as CSR arrays of its own run by the tile kernel through the nested handle `near`; the far
-    // part as the two streams and the bins of smvp_binned.hip
-    smvp::BinnedPlan bin;
-    smvp_csr *near = nullptr;
-    // BINNED with the window plan: pass A (it needs x only) goes onto a stream of its own, ahead of the near part, and
-    // the near part's workgroups take the CUs as pass A's last ones leave them
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    double far_share = -2.0;   // share of entries with |column - row| > kBinNearBand; -2: not measured yet
-    bool plain_only = false;   // a nested handle: AUTO stays on the tile kernels
-    int sweep_g = 0;           // COLSWEEP: chunks in flight per wavefront (fixed when the plan is built)
+    bool tile_chosen = false;           // the caller named the tile size (smvp_csr_set_kernel param): the plan keeps it
+    double spread = -2.0;     // share of gathers that pull their own line of x (csr_gather_spread); -2: not measured yet
+    double far_share = -2.0;  // share of entries with |column - row| > kBinNearBand; -2: not measured yet
     double plan_build_ms = 0.0;  // host wall time of the last plan build
-    // smvp_csr_spmm (K7, smvp_spmm.hip): the rows ordered by length inside blocks of kSpmmBlockRows, built by the first call
-    // and kept whatever the SpMV plan is (it depends on row_ptr only)
-    int *d_spmm_order = nullptr;
-    bool spmm_planned = false;
-    double spmm_build_ms = 0.0;
+
+    TilePlan tile;
+    SweepPlan sweep;
+    BinnedSide binned;
+    SpmmPlan spmm;
 };
 
 namespace {
 
-void free_binned(smvp_csr *h)
+void free_tile_plan(TilePlan *p)
 {
-    smvp_csr_destroy(h->near);
-    h->near = nullptr;
-    smvp::free_binned_plan(&h->bin);
-    if (h->side)
-        (void)hipStreamDestroy(h->side);
-    if (h->ev_fork)
-        (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join)
-        (void)hipEventDestroy(h->ev_join);
-    h->side = nullptr;
-    h->ev_fork = h->ev_join = nullptr;
+    for (void *q : {(void *)p->d_tile_row, (void *)p->d_tile_next, (void *)p->d_col16, (void *)p->d_col_base, (void *)p->d_row_rel,
+                    (void *)p->d_carry_row, (void *)p->d_carry, (void *)p->d_pos_sorted, (void *)p->d_meta, (void *)p->d_ovf_ptr,
+                    (void *)p->d_ovf_k, (void *)p->d_ovf_val, (void *)p->d_cache_ptr, (void *)p->d_val_cache, (void *)p->d_group_run,
+                    (void *)p->d_word32, (void *)p->d_run_ptr, (void *)p->d_run_tab})
+        if (q)
+            (void)hipFree(q);
+    *p = TilePlan{};
 }
 
-void free_sweep_plan(smvp_csr *h)
+void free_sweep_plan(SweepPlan *p)
 {
-    for (void *p : {(void *)h->d_sweep_ptr, (void *)h->d_sweep_col, (void *)h->d_sweep_val, (void *)h->d_sweep_row, (void *)h->d_sweep_part})
-        if (p)
-            (void)hipFree(p);
-    h->d_sweep_part = nullptr;
-    h->d_sweep_ptr = nullptr;
-    h->d_sweep_col = nullptr;
-    h->d_sweep_val = nullptr;
-    h->d_sweep_row = nullptr;
+    for (void *q : {(void *)p->d_ptr, (void *)p->d_col, (void *)p->d_val, (void *)p->d_row, (void *)p->d_part})
+        if (q)
+            (void)hipFree(q);
+    *p = SweepPlan{};
 }
+
+void free_binned_side(BinnedSide *p)
+{
+    smvp_csr_destroy(p->near);
+    smvp::free_binned_plan(&p->bin);
+    if (p->side)
+        (void)hipStreamDestroy(p->side);
+    for (hipEvent_t e : {p->ev_fork, p->ev_join})
+        if (e)
+            (void)hipEventDestroy(e);
+    *p = BinnedSide{};
+}
+
+void free_spmm_plan(SpmmPlan *p)
+{
+    if (p->d_order)
+        (void)hipFree(p->d_order);
+    *p = SpmmPlan{};
+}
+
+// the derived quantities the plans are read through
+inline bool tile_ordered(int flavor) { return flavor == smvp::kFlavorTjdsS || flavor == smvp::kFlavorTjdsH; }
+inline bool runs_on_tile_plan(int k) { return k != SMVP_CSR_KERNEL_VECTOR && k != SMVP_CSR_KERNEL_COLSWEEP && k != SMVP_CSR_KERNEL_BINNED; }
+inline int owner_flavor(const smvp_csr *h) { return h->tile.d_col16 ? smvp::kFlavorCsr16 : h->flavor; }  // what the owner kernel is launched with
+inline double csr_matrix_bytes(const smvp_csr *h) { return 12.0 * h->nnz + 4.0 * (h->rows + 1.0); }
+// rows of one strip of the column sweep: a workgroup's kSweepWaves wavefronts share rb rows, or rb * parts where every strip is cut
+// into column parts (one wavefront each); XCD-private parts run on whole strips
+inline int sweep_strip_rows(const SweepPlan &s) { return (s.parts == smvp::kSweepXcdParts ? s.rb : s.rb * s.parts) / smvp::kSweepWaves; }
 
 // Rows per workgroup of the column sweep (four strips) and how many workgroups start together.  A block of rb rows streams
 // rb * (mean row length) entries in column order, 1024 per pass of its workgroup (256 per strip), so its window moves
@@ -320,10 +372,11 @@ bool sweep_param_ok(int param)
 
 int build_sweep_plan(smvp_csr *h, int want)
 {
-    free_sweep_plan(h);
+    SweepPlan &s = h->sweep;
+    free_sweep_plan(&s);
     const int want_rb = sweep_param_rb(want);
-    h->sweep_parts = sweep_param_parts(want);
-    const bool xcd = h->sweep_parts == smvp::kSweepXcdParts;
+    s.parts = sweep_param_parts(want);
+    const bool xcd = s.parts == smvp::kSweepXcdParts;
     if (xcd) {
         // XCD-private column parts (SMVP_CSR_SWEEP_PARTS(rb, 8)): a generation of 256 workgroups = 32 row groups x 8 parts; the height is the
         // caller's, or the one that cuts the rows into whole generations with the tallest strips the LDS takes
@@ -333,27 +386,27 @@ int build_sweep_plan(smvp_csr *h, int want)
             const long long gens = std::max<long long>(1, ((long long)h->rows + per_gen_max - 1) / per_gen_max);
             rb = (int)std::min<long long>(kSweepMaxRb, std::max<long long>(256, (((long long)h->rows + 32 * gens - 1) / (32 * gens) + 3) / 4 * 4));
         }
-        h->sweep_rb = rb;
-        h->sweep_per_launch = 256;
+        s.rb = rb;
+        s.per_launch = 256;
     } else {
-        choose_sweep_shape(h->rows, h->cols, h->nnz, want_rb, &h->sweep_rb, &h->sweep_per_launch);
-        while (h->sweep_parts > 1 && (long long)h->sweep_rb * h->sweep_parts > kSweepMaxRb)
-            h->sweep_parts >>= 1;  // (a chosen height may leave room for fewer parts than asked)
+        choose_sweep_shape(h->rows, h->cols, h->nnz, want_rb, &s.rb, &s.per_launch);
+        while (s.parts > 1 && (long long)s.rb * s.parts > kSweepMaxRb)
+            s.parts >>= 1;  // (a chosen height may leave room for fewer parts than asked)
     }
-    const int strip_rows = xcd ? h->sweep_rb / smvp::kSweepWaves : h->sweep_rb * h->sweep_parts / smvp::kSweepWaves;
-    h->sweep_g = smvp::sweep_chunks_in_flight(strip_rows, sweep_param_chunks(want));
+    const int strip_rows = sweep_strip_rows(s);
+    s.g = smvp::sweep_chunks_in_flight(strip_rows, sweep_param_chunks(want));
     if (const hipError_t pe = smvp::prepare_csr_colsweep(); pe != hipSuccess)
         return smvp::fail(SMVP_ERR_HIP, "the column sweep cannot have its LDS: %s", hipGetErrorString(pe));
     const int nstrips = (h->rows + strip_rows - 1) / strip_rows;
     const size_t n = (size_t)std::max(h->nnz, 4);
-    if (hipMalloc((void **)&h->d_sweep_ptr, ((size_t)nstrips * h->sweep_parts + 2) * sizeof(long long)) != hipSuccess ||
-        hipMalloc((void **)&h->d_sweep_col, n * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&h->d_sweep_val, n * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&h->d_sweep_row, n * sizeof(unsigned short)) != hipSuccess ||
-        (xcd && hipMalloc((void **)&h->d_sweep_part, sizeof(double) * smvp::kSweepXcdParts * (size_t)std::max(h->rows, 1)) != hipSuccess))
+    if (hipMalloc((void **)&s.d_ptr, ((size_t)nstrips * s.parts + 2) * sizeof(long long)) != hipSuccess ||
+        hipMalloc((void **)&s.d_col, n * sizeof(int)) != hipSuccess ||
+        hipMalloc((void **)&s.d_val, n * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&s.d_row, n * sizeof(unsigned short)) != hipSuccess ||
+        (xcd && hipMalloc((void **)&s.d_part, sizeof(double) * smvp::kSweepXcdParts * (size_t)std::max(h->rows, 1)) != hipSuccess))
         return smvp::fail(SMVP_ERR_ALLOC, "cannot allocate the column-sweep plan (%d entries)", h->nnz);
-    return smvp::build_colsweep_plan(h->d_row_ptr, h->d_col_ind, h->d_val, h->rows, h->cols, h->nnz, strip_rows, h->sweep_parts, smvp::kSweepChunk,
-                                     smvp::kSweepRowBits, smvp::kSweepTurnCap, h->d_sweep_ptr, h->d_sweep_col, h->d_sweep_val, h->d_sweep_row, nullptr);
+    return smvp::build_colsweep_plan(h->d_row_ptr, h->d_col_ind, h->d_val, h->rows, h->cols, h->nnz, strip_rows, s.parts, smvp::kSweepChunk,
+                                     smvp::kSweepRowBits, smvp::kSweepTurnCap, s.d_ptr, s.d_col, s.d_val, s.d_row, nullptr);
 }
 
 // Share of the gathers of a (large) CSR matrix that pull their own 128-byte line of x through the L2, estimated on
@@ -394,6 +447,29 @@ double csr_gather_spread(const smvp_csr *h)
 //    (profiles/r02_colsweep_measured.txt);
 //  * no row is so long that its strip becomes the critical path; the matrix is worth a second copy (>= 4 M entries).
 constexpr double kSweepMinSpread = 0.6;
+
+// the two figures AUTO's choice rests on, measured when first asked for and kept until a re-plan forgets them (-1: not available)
+double measured_spread(smvp_csr *h)
+{
+    if (h->spread < -1.5)
+        h->spread = h->flavor == smvp::kFlavorCsr ? csr_gather_spread(h) : -1.0;
+    return h->spread;
+}
+
+double measured_far_share(smvp_csr *h)
+{
+    if (h->far_share < -1.5) {
+        double share = -1.0;
+        if (h->flavor != smvp::kFlavorCsr ||
+            smvp::csr_far_share(h->d_row_ptr, h->d_col_ind, h->rows, h->nnz, smvp::kBinNearBand, h->row0, &share, nullptr) != SMVP_OK) {
+            (void)hipGetLastError();
+            share = -1.0;
+        }
+        h->far_share = share;
+    }
+    return h->far_share;
+}
+
 bool sweep_suits(smvp_csr *h)
 {
     if (h->plain_only || h->flavor != smvp::kFlavorCsr || h->nnz < 4 * 1024 * 1024 || h->rows < 4096)
@@ -402,9 +478,7 @@ bool sweep_suits(smvp_csr *h)
     if (mean < 4.0 || (double)h->cols * 8.0 < 8.0 * 1024 * 1024 || 8192.0 * mean * 160.0 < (double)h->cols ||
         (double)h->max_row_len > 256.0 * mean)
         return false;
-    if (h->spread < -1.5)
-        h->spread = csr_gather_spread(h);
-    return h->spread >= kSweepMinSpread;
+    return measured_spread(h) >= kSweepMinSpread;
 }
 
 // AUTO picks the binned plan (near part on the tile kernel, far part in two LDS-binned passes: smvp_binned.hip) where the
@@ -422,55 +496,7 @@ bool binned_suits(smvp_csr *h)
     if (h->plain_only || h->flavor != smvp::kFlavorCsr || h->nnz < 4 * 1024 * 1024 || h->rows < 4096 ||
         (double)h->cols * 8.0 < 16.0 * 1024 * 1024)
         return false;
-    if (h->spread < -1.5)
-        h->spread = csr_gather_spread(h);
-    if (h->spread < kBinnedMinSpread)
-        return false;
-    if (h->far_share < -1.5) {
-        double share = -1.0;
-        if (smvp::csr_far_share(h->d_row_ptr, h->d_col_ind, h->rows, h->nnz, smvp::kBinNearBand, h->row0, &share, nullptr) != SMVP_OK) {
-            (void)hipGetLastError();
-            share = -1.0;
-        }
-        h->far_share = share;
-    }
-    return h->far_share >= kBinnedMinFarShare;
-}
-
-void free_stream_plan(smvp_csr *h)
-{
-    if (h->d_tile_row)
-        (void)hipFree(h->d_tile_row);
-    if (h->d_carry_row)
-        (void)hipFree(h->d_carry_row);
-    if (h->d_carry)
-        (void)hipFree(h->d_carry);
-    if (h->d_tile_next)
-        (void)hipFree(h->d_tile_next);
-    if (h->d_col16)
-        (void)hipFree(h->d_col16);
-    if (h->d_col_base)
-        (void)hipFree(h->d_col_base);
-    if (h->d_row_rel)
-        (void)hipFree(h->d_row_rel);
-    h->d_col16 = nullptr;
-    h->d_col_base = nullptr;
-    h->d_row_rel = nullptr;
-    for (void *p : {(void *)h->d_pos_sorted, (void *)h->d_meta, (void *)h->d_ovf_ptr, (void *)h->d_ovf_val, (void *)h->d_ovf_k,
-                    (void *)h->d_cache_ptr, (void *)h->d_val_cache, (void *)h->d_word32, (void *)h->d_group_run,
-                    (void *)h->d_run_ptr, (void *)h->d_run_tab})
-        if (p)
-            (void)hipFree(p);
-    h->d_pos_sorted = h->d_meta = h->d_ovf_ptr = h->d_ovf_k = h->d_cache_ptr = nullptr;
-    h->d_ovf_val = nullptr;
-    h->d_run_ptr = h->d_run_tab = nullptr;
-    h->d_group_run = nullptr;
-    h->d_word32 = nullptr;
-    h->d_val_cache = nullptr;
-    h->cached_total = h->runs_total = 0;
-    h->d_tile_row = h->d_carry_row = h->d_tile_next = nullptr;
-    h->d_carry = nullptr;
-    h->ntiles = 0;
+    return measured_spread(h) >= kBinnedMinSpread && measured_far_share(h) >= kBinnedMinFarShare;
 }
 
 // tile_row[b]  = first row whose first entry lies at or after b*TILE
@@ -490,28 +516,30 @@ void try_column_offsets(smvp_csr *h)
         tiles.push_back(2048);                           // 2048-entry tiles: 0.0220 / 0.0364 / 0.0851 against 0.0219 / 0.0345 / 0.0787 ms
     tiles.push_back(smvp::kStreamBlock * h->vpt);
     const size_t max_tiles = ((size_t)h->nnz + 1023) / 1024 + 1;
-    if (hipMalloc((void **)&h->d_col_base, max_tiles * sizeof(int)) == hipSuccess &&
-        hipMalloc((void **)&h->d_col16, ((size_t)h->nnz + 8) * sizeof(unsigned short)) == hipSuccess) {
+    int *col_base = nullptr;
+    unsigned short *col16 = nullptr;
+    if (hipMalloc((void **)&col_base, max_tiles * sizeof(int)) == hipSuccess &&
+        hipMalloc((void **)&col16, ((size_t)h->nnz + 8) * sizeof(unsigned short)) == hipSuccess) {
         for (int tile : tiles) {
             int fits = 0;
-            if (smvp::build_column_offsets(h->d_col_ind, h->nnz, tile, h->d_col_base, h->d_col16, &fits, nullptr) == SMVP_OK && fits) {
+            if (smvp::build_column_offsets(h->d_col_ind, h->nnz, tile, col_base, col16, &fits, nullptr) == SMVP_OK && fits) {
                 h->vpt = tile / smvp::kStreamBlock;
+                h->tile.d_col_base = col_base;
+                h->tile.d_col16 = col16;
                 return;
             }
         }
     }
     (void)hipGetLastError();  // no second copy: the kernel reads col_ind itself
-    if (h->d_col16)
-        (void)hipFree(h->d_col16);
-    if (h->d_col_base)
-        (void)hipFree(h->d_col_base);
-    h->d_col16 = nullptr;
-    h->d_col_base = nullptr;
+    for (void *p : {(void *)col16, (void *)col_base})
+        if (p)
+            (void)hipFree(p);
 }
 
-int build_stream_plan(smvp_csr *h)
+int build_tile_plan(smvp_csr *h)
 {
-    free_stream_plan(h);
+    TilePlan &t = h->tile;
+    free_tile_plan(&t);
     try_column_offsets(h);
     const int tile = smvp::kStreamBlock * h->vpt;
     const long long nnz = h->nnz;
@@ -531,10 +559,10 @@ int build_stream_plan(smvp_csr *h)
     tile_row[(size_t)ntiles] = h->rows;
     for (int b = 0; b < ntiles; ++b)
         tile_next[(size_t)b] = rp[tile_row[(size_t)b + 1]];
-    if (int rc = upload(&h->d_tile_row, tile_row))
+    if (int rc = upload(&t.d_tile_row, tile_row))
         return rc;
     if (h->kernel == SMVP_CSR_KERNEL_STREAM) {
-        if (int rc = upload(&h->d_tile_next, tile_next))
+        if (int rc = upload(&t.d_tile_next, tile_next))
             return rc;
         if (h->rows > 0 && smvp::option("csr_rowrel", 1) != 0) {  // (plan option: 0 = keep row_ptr)
             std::vector<unsigned short> rel((size_t)h->rows);
@@ -543,17 +571,17 @@ int build_stream_plan(smvp_csr *h)
                 for (int rr = tile_row[(size_t)b]; rr < tile_row[(size_t)b + 1]; ++rr)
                     rel[(size_t)rr] = (unsigned short)(rp[rr] - s0);  // 0 ... tile (tile: trailing rows without entries)
             }
-            if (int rc = upload(&h->d_row_rel, rel))
+            if (int rc = upload(&t.d_row_rel, rel))
                 return rc;
         }
     } else {
-        if (int rc = upload(&h->d_carry_row, carry_row))
+        if (int rc = upload(&t.d_carry_row, carry_row))
             return rc;
-        HIP_TRY(hipMalloc((void **)&h->d_carry, std::max(ntiles, 1) * sizeof(double)));
-        HIP_TRY(hipMemset(h->d_carry, 0, std::max(ntiles, 1) * sizeof(double)));
+        HIP_TRY(hipMalloc((void **)&t.d_carry, std::max(ntiles, 1) * sizeof(double)));
+        HIP_TRY(hipMemset(t.d_carry, 0, std::max(ntiles, 1) * sizeof(double)));
     }
-    h->ntiles = ntiles;
-    if (h->flavor == smvp::kFlavorTjdsS || h->flavor == smvp::kFlavorTjdsH) {
+    t.ntiles = ntiles;
+    if (tile_ordered(h->flavor)) {
         // every tile's entries in TJDS order + what each tile reads past its end, in row order
         std::vector<int> ovf_ptr((size_t)ntiles + 1, 0);
         for (int b = 0; b < ntiles; ++b) {
@@ -562,34 +590,29 @@ int build_stream_plan(smvp_csr *h)
             ovf_ptr[(size_t)b + 1] = ovf_ptr[(size_t)b] + (owns ? (int)(tile_next[(size_t)b] - e) : 0);
         }
         const int total = ovf_ptr[(size_t)ntiles];
-        h->ovf_total = total;
-        if (int rc = upload(&h->d_ovf_ptr, ovf_ptr))
+        t.ovf_total = total;
+        if (int rc = upload(&t.d_ovf_ptr, ovf_ptr))
             return rc;
         const size_t n = (size_t)std::max(h->nnz, 4), m = (size_t)std::max(total, 4);
-        if (hipMalloc((void **)&h->d_ovf_val, m * sizeof(double)) != hipSuccess ||
-            hipMalloc((void **)&h->d_ovf_k, m * sizeof(int)) != hipSuccess ||
-            hipMalloc((void **)&h->d_cache_ptr, ((size_t)ntiles + 2) * sizeof(int)) != hipSuccess)
+        const bool half = h->flavor == smvp::kFlavorTjdsH;
+        const TjdsSource &src = h->src;
+        // (the last two: the flavour's index word per entry and its second array -- TjdsH word32 and the tiles' run_ptr, TjdsS
+        // pos_sorted and meta)
+        if (hipMalloc((void **)&t.d_ovf_val, m * sizeof(double)) != hipSuccess ||
+            hipMalloc((void **)&t.d_ovf_k, m * sizeof(int)) != hipSuccess ||
+            hipMalloc((void **)&t.d_cache_ptr, ((size_t)ntiles + 2) * sizeof(int)) != hipSuccess ||
+            hipMalloc(half ? (void **)&t.d_word32 : (void **)&t.d_pos_sorted, n * sizeof(int)) != hipSuccess ||
+            hipMalloc(half ? (void **)&t.d_run_ptr : (void **)&t.d_meta, (half ? (size_t)ntiles + 2 : n) * sizeof(int)) != hipSuccess)
             return smvp::fail(SMVP_ERR_ALLOC, "cannot allocate the tile-ordered TJDS streams");
-        if (h->flavor == smvp::kFlavorTjdsH) {
-            if (hipMalloc((void **)&h->d_word32, n * sizeof(unsigned)) != hipSuccess ||
-                hipMalloc((void **)&h->d_run_ptr, ((size_t)ntiles + 2) * sizeof(int)) != hipSuccess)
-                return smvp::fail(SMVP_ERR_ALLOC, "cannot allocate the tile-ordered TJDS streams");
-            if (int rc = smvp::build_tile_half_streams(h->d_pos, h->nnz, tile, h->d_start_pos, h->num_diag, h->d_val,
-                                                       h->cache_min_tiles, h->d_word32, h->d_cache_ptr,
-                                                       h->d_run_ptr, &h->d_val_cache, &h->d_run_tab, &h->d_group_run,
-                                                       &h->cached_total, &h->runs_total, nullptr))
-                return rc;
-        } else {
-            if (hipMalloc((void **)&h->d_pos_sorted, n * sizeof(int)) != hipSuccess ||
-                hipMalloc((void **)&h->d_meta, n * sizeof(int)) != hipSuccess)
-                return smvp::fail(SMVP_ERR_ALLOC, "cannot allocate the tile-ordered TJDS streams");
-            if (int rc = smvp::sort_tile_windows(h->d_pos, h->nnz, tile, h->d_start_pos, h->num_diag, smvp::kSlotBits, h->d_val,
-                                                 h->cache_min_tiles, h->d_pos_sorted, h->d_meta, h->d_cache_ptr, &h->d_val_cache,
-                                                 &h->cached_total, nullptr))
-                return rc;
-        }
-        if (int rc = smvp::build_tile_overflow(h->d_pos, h->d_ovf_ptr, total, ntiles, tile, h->nnz, h->d_start_pos,
-                                               h->num_diag, h->d_val, h->d_ovf_val, h->d_ovf_k, h->unit_operand ? 1 : 0, nullptr))
+        if (int rc = half ? smvp::build_tile_half_streams(src.pos, h->nnz, tile, src.start_pos, src.num_diag, h->d_val, h->cache_min_tiles,
+                                                          t.d_word32, t.d_cache_ptr, t.d_run_ptr, &t.d_val_cache, &t.d_run_tab,
+                                                          &t.d_group_run, &t.cached_total, &t.runs_total, nullptr)
+                          : smvp::sort_tile_windows(src.pos, h->nnz, tile, src.start_pos, src.num_diag, smvp::kSlotBits, h->d_val,
+                                                    h->cache_min_tiles, t.d_pos_sorted, t.d_meta, t.d_cache_ptr, &t.d_val_cache,
+                                                    &t.cached_total, nullptr))
+            return rc;
+        if (int rc = smvp::build_tile_overflow(src.pos, t.d_ovf_ptr, total, ntiles, tile, h->nnz, src.start_pos, src.num_diag, h->d_val,
+                                               t.d_ovf_val, t.d_ovf_k, src.unit_operand ? 1 : 0, nullptr))
             return rc;
     }
     return SMVP_OK;
@@ -638,7 +661,7 @@ bool choose_csr_kernel(smvp_csr *h, int kernel, int param)
         h->tile_chosen = param > 0;
         if (tile == 0) {  // 1024 measured 1-4 % ahead of 2048 on memplus x944 and pwt x459; 256-entry tiles when
             tile = (kernel == SMVP_CSR_KERNEL_STREAM && h->nnz < 512 * 1024) ? 256 : 1024;  // 1024 would leave CUs idle
-            if ((h->flavor == smvp::kFlavorTjdsS || h->flavor == smvp::kFlavorTjdsH) && tile == 1024 && h->nnz >= 12 * 1024 * 1024)
+            if ((tile_ordered(h->flavor)) && tile == 1024 && h->nnz >= 12 * 1024 * 1024)
                 tile = 2048;  // more entries per val line inside a tile.  With the value cache and the 16-bit second word (round 3),
                               // memplus x59 / x118 / x236 / x472 (7.4 / 14.9 / 29.8 / 59.5 M entries), 1024 against 2048:
                               // 0.0285 / 0.0530 / 0.1157 / 0.2327 against 0.0280 / 0.0493 / 0.1070 / 0.2151 ms
@@ -650,27 +673,81 @@ bool choose_csr_kernel(smvp_csr *h, int kernel, int param)
 
 }  // namespace
 
-// what a TJDS flavour borrows from its smvp_tjds owner (set before the tile plan is built)
-struct TjdsSource {
-    const int *pos = nullptr;
-    const int *start_pos = nullptr;
-    int num_diag = 0;
-    // the two-phase product's second phase: `val` holds the products of the first phase (written anew before every launch: no value
-    // cache, overflow entries by position), the operand is the unit vector (no x gather)
-    bool unit_operand = false;
-};
+// (declared ahead of its definition: the binned plan nests a handle of its own for the near part)
+static int csr_create_impl(smvp_csr_t **out, int device, int rows, int cols, int nnz, const int *row_ptr, const int *col_ind, const double *val,
+                           int mem_kind, const int *host_row_ptr, int flavor, const TjdsSource *src = nullptr, bool plain_only = false,
+                           long long first_row = 0);
 
-static int build_binned(smvp_csr *h, int band);
-static double wall_ms();
+// The binned plan: near / far split on the device; the near part as the window plan (smvp_near_window.hip) where that suits,
+// else behind a nested handle that stays on the tile kernels.
+static int build_binned(smvp_csr *h, int band)
+{
+    free_binned_side(&h->binned);
+    // both passes (and K6) ask for more than 64 KB of dynamic LDS: a device that refuses makes the PLAN fail here -- AUTO then
+    // falls back to the tile kernel (plan_csr) -- instead of every later product
+    if (hipError_t le = smvp::binned_reserve_lds(); le != hipSuccess) {
+        (void)hipGetLastError();
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "the binned plan needs 154 KB of LDS per workgroup: %s", hipGetErrorString(le));
+    }
+    const bool window = smvp::option("binned_near", 0) == 0;  // (plan option: 1 keeps the near part on the tile kernel)
+    if (int rc = smvp::build_binned_plan(h->d_row_ptr, h->d_col_ind, h->d_val, h->rows, h->cols, h->nnz, band, h->row0, window, &h->binned.bin, nullptr))
+        return rc;
+    if (h->binned.bin.nw.on) {
+        if (smvp::option("binned_overlap", 1) != 0 && h->binned.bin.nf > 0) {  // (plan option: 0 = pass A behind the near part, one stream)
+            HIP_TRY(hipStreamCreateWithFlags(&h->binned.side, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&h->binned.ev_fork, hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&h->binned.ev_join, hipEventDisableTiming));
+        }
+        return SMVP_OK;
+    }
+    return csr_create_impl(&h->binned.near, h->device, h->rows, h->cols, h->binned.bin.nnz_near, h->binned.bin.near_ptr, h->binned.bin.near_col, h->binned.bin.near_val,
+                           SMVP_MEM_DEVICE, nullptr, smvp::kFlavorCsr, nullptr, true, h->row0);
+}
 
-static int csr_create_impl(smvp_csr_t **out, int device, int rows, int cols, int nnz,
-                           const int *row_ptr, const int *col_ind, const double *val,
-                           int mem_kind, const int *host_row_ptr, int flavor, const TjdsSource *src = nullptr,
-                           bool plain_only = false, long long first_row = 0)
+// Plans a handle: resolves `kernel` (choose_csr_kernel: a `param` the resolved kernel rejects changes nothing), releases the
+// plans the resolved kernel does not use, builds the one it does -- VECTOR has none -- and records plan_build_ms.  Where the
+// second copy of the entries that COLSWEEP and BINNED keep does not fit (or cannot be built) the handle goes back to the tile
+// kernel, which needs none: silently at creation (AUTO's choice; only the tile plan's own failure is an error), with the error
+// still reported from smvp_csr_set_kernel -- the handle stays usable, and if even the tile plan fails it is left without a
+// plan, which smvp_csr_spmv refuses.
+static int plan_csr(smvp_csr *h, int kernel, int param, bool silent_fallback)
+{
+    if (!choose_csr_kernel(h, kernel, param))
+        return smvp::fail(SMVP_ERR_INVALID, "entries per tile must be 256 (stream only), 1024 or 2048 for the kernel "
+                                            "this matrix resolves to (column sweep: 256 ... 20480 rows per block, a multiple of 4; binned: the near band, >= 0)");
+    const double t0 = wall_ms();
+    free_sweep_plan(&h->sweep);
+    free_binned_side(&h->binned);
+    int rc = SMVP_OK;
+    if (runs_on_tile_plan(h->kernel)) {
+        rc = build_tile_plan(h);
+    } else {
+        free_tile_plan(&h->tile);
+        if (h->kernel != SMVP_CSR_KERNEL_VECTOR)
+            rc = h->kernel == SMVP_CSR_KERNEL_COLSWEEP ? build_sweep_plan(h, param) : build_binned(h, param);
+        if (rc != SMVP_OK) {
+            const std::string why = smvp_last_error();
+            (void)hipGetLastError();
+            free_sweep_plan(&h->sweep);
+            free_binned_side(&h->binned);
+            h->spread = -1.0;
+            choose_csr_kernel(h, SMVP_CSR_KERNEL_STREAM, 0);
+            const int tile_rc = build_tile_plan(h);
+            if (tile_rc != SMVP_OK)
+                free_tile_plan(&h->tile);
+            rc = silent_fallback ? tile_rc : smvp::fail(rc, "%s", why.c_str());
+        }
+    }
+    h->plan_build_ms = wall_ms() - t0;
+    return rc;
+}
+
+static int csr_create_impl(smvp_csr_t **out, int device, int rows, int cols, int nnz, const int *row_ptr, const int *col_ind, const double *val,
+                           int mem_kind, const int *host_row_ptr, int flavor, const TjdsSource *src, bool plain_only, long long first_row)
 {
     const bool plain = flavor == smvp::kFlavorCsr;
     if (!out || rows < 0 || cols < 0 || nnz < 0 || !row_ptr ||
-        (nnz > 0 && ((!col_ind && flavor != smvp::kFlavorTjdsS && flavor != smvp::kFlavorTjdsH) || !val)))
+        (nnz > 0 && ((!col_ind && !tile_ordered(flavor)) || !val)))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_create: bad argument");
     if (mem_kind != SMVP_MEM_HOST && mem_kind != SMVP_MEM_DEVICE)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_create: bad mem_kind");
@@ -685,13 +762,10 @@ static int csr_create_impl(smvp_csr_t **out, int device, int rows, int cols, int
     h->flavor = flavor;
     h->plain_only = plain_only;
     h->row0 = first_row;
-    if (src) {
-        h->d_pos = src->pos, h->d_start_pos = src->start_pos;
-        h->num_diag = src->num_diag;
-        h->unit_operand = src->unit_operand;
-        if (h->unit_operand)
-            h->cache_min_tiles = 0;
-    }
+    if (src)
+        h->src = *src;
+    if (h->src.unit_operand)
+        h->cache_min_tiles = 0;
     h->rows = rows, h->cols = cols, h->nnz = nnz;
     h->h_row_ptr.resize((size_t)rows + 1);
     int rc = SMVP_OK;
@@ -732,19 +806,8 @@ static int csr_create_impl(smvp_csr_t **out, int device, int rows, int cols, int
     if (rc == SMVP_OK) {
         const double t0 = wall_ms();
         // every flavour but plain CSR exists for the owner-completes kernel only
-        choose_csr_kernel(h, plain ? SMVP_CSR_KERNEL_AUTO : SMVP_CSR_KERNEL_STREAM, 0);
-        if ((h->kernel == SMVP_CSR_KERNEL_COLSWEEP && build_sweep_plan(h, 0) != SMVP_OK) ||
-            (h->kernel == SMVP_CSR_KERNEL_BINNED && build_binned(h, 0) != SMVP_OK)) {
-            // AUTO's second copy of the entries did not fit: the tile kernel needs none
-            (void)hipGetLastError();
-            free_sweep_plan(h);
-            free_binned(h);
-            h->spread = -1.0;
-            choose_csr_kernel(h, SMVP_CSR_KERNEL_STREAM, 0);
-        }
-        if (h->kernel != SMVP_CSR_KERNEL_VECTOR && h->kernel != SMVP_CSR_KERNEL_COLSWEEP && h->kernel != SMVP_CSR_KERNEL_BINNED)
-            rc = build_stream_plan(h);
-        h->plan_build_ms = wall_ms() - t0;
+        rc = plan_csr(h, plain ? SMVP_CSR_KERNEL_AUTO : SMVP_CSR_KERNEL_STREAM, 0, true);
+        h->plan_build_ms = wall_ms() - t0;  // (with what AUTO measured to choose)
     }
     if (rc != SMVP_OK) {
         smvp_csr_destroy(h);
@@ -780,50 +843,8 @@ extern "C" int smvp_csr_far_share(smvp_csr_t *h, double *share)
     if (!h || !share)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_far_share: bad argument");
     DeviceScope on(h->device);
-    if (h->far_share < -1.5) {
-        double s = -1.0;
-        if (h->flavor != smvp::kFlavorCsr ||
-            smvp::csr_far_share(h->d_row_ptr, h->d_col_ind, h->rows, h->nnz, smvp::kBinNearBand, h->row0, &s, nullptr) != SMVP_OK) {
-            (void)hipGetLastError();
-            s = -1.0;
-        }
-        h->far_share = s;
-    }
-    *share = h->far_share;
+    *share = measured_far_share(h);
     return SMVP_OK;
-}
-
-static double wall_ms()
-{
-    timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
-}
-
-// The binned plan: near / far split on the device; the near part as the window plan (smvp_near_window.hip) where that suits,
-// else behind a nested handle that stays on the tile kernels.
-static int build_binned(smvp_csr *h, int band)
-{
-    free_binned(h);
-    // both passes (and K6) ask for more than 64 KB of dynamic LDS: a device that refuses makes the PLAN fail here -- AUTO then
-    // falls back to the tile kernel (csr_create_impl) -- instead of every later product
-    if (hipError_t le = smvp::binned_reserve_lds(); le != hipSuccess) {
-        (void)hipGetLastError();
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "the binned plan needs 154 KB of LDS per workgroup: %s", hipGetErrorString(le));
-    }
-    const bool window = smvp::option("binned_near", 0) == 0;  // (plan option: 1 keeps the near part on the tile kernel)
-    if (int rc = smvp::build_binned_plan(h->d_row_ptr, h->d_col_ind, h->d_val, h->rows, h->cols, h->nnz, band, h->row0, window, &h->bin, nullptr))
-        return rc;
-    if (h->bin.nw.on) {
-        if (smvp::option("binned_overlap", 1) != 0 && h->bin.nf > 0) {  // (plan option: 0 = pass A behind the near part, one stream)
-            HIP_TRY(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-        }
-        return SMVP_OK;
-    }
-    return csr_create_impl(&h->near, h->device, h->rows, h->cols, h->bin.nnz_near, h->bin.near_ptr, h->bin.near_col, h->bin.near_val,
-                           SMVP_MEM_DEVICE, nullptr, smvp::kFlavorCsr, nullptr, true, h->row0);
 }
 
 extern "C" int smvp_csr_set_kernel(smvp_csr_t *h, int kernel, int param)
@@ -841,37 +862,7 @@ extern "C" int smvp_csr_set_kernel(smvp_csr_t *h, int kernel, int param)
     // the documented re-plan after col_ind of adopted arrays changed in place: what AUTO measured belongs to the columns that
     // were there, so both figures are forgotten and taken again by whoever asks next (AUTO below, or the two getters)
     h->spread = h->far_share = -2.0;
-    if (!choose_csr_kernel(h, kernel, param))
-        return smvp::fail(SMVP_ERR_INVALID, "entries per tile must be 256 (stream only), 1024 or 2048 for the kernel "
-                                            "this matrix resolves to (column sweep: 256 ... 20480 rows per block, a multiple of 4; binned: the near band, >= 0)");
-    const double t0 = wall_ms();
-    free_sweep_plan(h);
-    free_binned(h);
-    int rc = SMVP_OK;
-    if (h->kernel == SMVP_CSR_KERNEL_COLSWEEP || h->kernel == SMVP_CSR_KERNEL_BINNED) {
-        free_stream_plan(h);
-        rc = h->kernel == SMVP_CSR_KERNEL_COLSWEEP ? build_sweep_plan(h, param) : build_binned(h, param);
-        if (rc != SMVP_OK) {
-            // the second copy of the entries did not fit (or could not be built): back to the tile kernel, which needs
-            // none, so that the handle stays usable -- the error is still reported
-            const std::string why = smvp_last_error();
-            (void)hipGetLastError();
-            free_sweep_plan(h);
-            free_binned(h);
-            h->spread = -1.0;
-            choose_csr_kernel(h, SMVP_CSR_KERNEL_STREAM, 0);
-            if (build_stream_plan(h) != SMVP_OK)
-                free_stream_plan(h);  // smvp_csr_spmv refuses a handle without a plan
-            h->plan_build_ms = wall_ms() - t0;
-            return smvp::fail(rc, "%s", why.c_str());
-        }
-    } else if (h->kernel != SMVP_CSR_KERNEL_VECTOR) {
-        rc = build_stream_plan(h);
-    } else {
-        free_stream_plan(h);
-    }
-    h->plan_build_ms = wall_ms() - t0;
-    return rc;
+    return plan_csr(h, kernel, param, false);
 }
 
 extern "C" int smvp_csr_get_kernel(const smvp_csr_t *h, int *kernel, int *param)
@@ -882,8 +873,8 @@ extern "C" int smvp_csr_get_kernel(const smvp_csr_t *h, int *kernel, int *param)
         *kernel = h->kernel;
     if (param)
         *param = h->kernel == SMVP_CSR_KERNEL_VECTOR ? h->lanes_per_row
-                 : h->kernel == SMVP_CSR_KERNEL_COLSWEEP ? (h->sweep_rb | ((h->sweep_parts == 8 ? 3 : h->sweep_parts == 4 ? 2 : h->sweep_parts == 2 ? 1 : 0) << kSweepPartsShift))
-                 : h->kernel == SMVP_CSR_KERNEL_BINNED   ? h->bin.band
+                 : h->kernel == SMVP_CSR_KERNEL_COLSWEEP ? (h->sweep.rb | ((h->sweep.parts == 8 ? 3 : h->sweep.parts == 4 ? 2 : h->sweep.parts == 2 ? 1 : 0) << kSweepPartsShift))
+                 : h->kernel == SMVP_CSR_KERNEL_BINNED   ? h->binned.bin.band
                                                          : h->vpt * smvp::kStreamBlock;
     return SMVP_OK;
 }
@@ -893,9 +884,7 @@ extern "C" int smvp_csr_gather_spread(smvp_csr_t *h, double *spread)
     if (!h || !spread)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_gather_spread: bad argument");
     DeviceScope on(h->device);
-    if (h->spread < -1.5)
-        h->spread = h->flavor == smvp::kFlavorCsr ? csr_gather_spread(h) : -1.0;
-    *spread = h->spread;
+    *spread = measured_spread(h);
     return SMVP_OK;
 }
 
@@ -903,38 +892,38 @@ static void fill_owner_launch(const smvp_csr_t *h, const double *d_x, double *d_
 {
     smvp::OwnerLaunch &l = *out;
     l.row_ptr = h->d_row_ptr, l.col_ind = h->d_col_ind, l.val = h->d_val, l.x = d_x, l.y = d_y;
-    l.tile_row = h->d_tile_row, l.tile_next = h->d_tile_next;
-    l.pos = h->d_pos, l.start_pos = h->d_start_pos;
-    if (h->flavor == smvp::kFlavorTjdsS || h->flavor == smvp::kFlavorTjdsH) {
-        l.pos = h->d_pos_sorted, l.col_ind = h->d_meta;
-        l.ovf_ptr = h->d_ovf_ptr, l.ovf_val = h->d_ovf_val, l.ovf_k = h->d_ovf_k;
-        l.cache_ptr = h->d_cache_ptr, l.val_cache = h->d_val_cache;
-        l.word32 = h->d_word32, l.group_run = h->d_group_run, l.run_ptr = h->d_run_ptr, l.run_tab = h->d_run_tab;
+    l.tile_row = h->tile.d_tile_row, l.tile_next = h->tile.d_tile_next;
+    l.pos = h->src.pos, l.start_pos = h->src.start_pos;
+    if (tile_ordered(h->flavor)) {
+        l.pos = h->tile.d_pos_sorted, l.col_ind = h->tile.d_meta;
+        l.ovf_ptr = h->tile.d_ovf_ptr, l.ovf_val = h->tile.d_ovf_val, l.ovf_k = h->tile.d_ovf_k;
+        l.cache_ptr = h->tile.d_cache_ptr, l.val_cache = h->tile.d_val_cache;
+        l.word32 = h->tile.d_word32, l.group_run = h->tile.d_group_run, l.run_ptr = h->tile.d_run_ptr, l.run_tab = h->tile.d_run_tab;
     }
     l.stamps = stamps;
-    l.rows = h->rows, l.nnz = h->nnz, l.ntiles = h->ntiles;
-    l.col16 = h->d_col16, l.col_base = h->d_col_base;
-    l.row_rel = h->d_row_rel;
-    l.unit_x = h->unit_operand ? 1 : 0;
+    l.rows = h->rows, l.nnz = h->nnz, l.ntiles = h->tile.ntiles;
+    l.col16 = h->tile.d_col16, l.col_base = h->tile.d_col_base;
+    l.row_rel = h->tile.d_row_rel;
+    l.unit_x = h->src.unit_operand ? 1 : 0;
 }
 
 // `reps` products of the tile kernel in ONE launch, each product's window stamped (csr_stream_owner_repeat); grid from
-// csr_repeat_grid.  The products are those of csr_spmv_impl, bit for bit: the same kernel body walks the same tiles.
-static int csr_repeat_grid(const smvp_csr_t *h)
+// csr_repeat_grid.  The products are those of csr_spmv_stamped, bit for bit: the same kernel body walks the same tiles.
+int smvp::csr_repeat_grid(const smvp_csr_t *h)
 {
-    if (!h || h->kernel != SMVP_CSR_KERNEL_STREAM || !h->d_tile_row || h->rows <= 0)
+    if (!h || h->kernel != SMVP_CSR_KERNEL_STREAM || !h->tile.d_tile_row || h->rows <= 0)
         return 0;
     DeviceScope on(h->device);
-    return smvp::owner_repeat_grid(h->vpt, h->d_col16 ? smvp::kFlavorCsr16 : h->flavor, h->ntiles);
+    return smvp::owner_repeat_grid(h->vpt, owner_flavor(h), h->tile.ntiles);
 }
 
-static int csr_spmv_repeat(smvp_csr_t *h, const double *d_x, double *d_y, void *stream, unsigned long long *stamps, int reps, int grid,
-                           unsigned *ctl_words, bool first_of_run, unsigned long long patience)
+int smvp::csr_spmv_repeat(smvp_csr_t *h, const double *d_x, double *d_y, void *stream, unsigned long long *stamps, int reps, int grid,
+                          unsigned *ctl_words, bool first_of_run, unsigned long long patience)
 {
     DeviceScope on(h->device);
     smvp::OwnerLaunch l{};
     fill_owner_launch(h, d_x, d_y, stamps, &l);
-    const hipError_t e = smvp::launch_csr_stream_owner_repeat(h->vpt, h->d_col16 ? smvp::kFlavorCsr16 : h->flavor, l, reps, grid, ctl_words,
+    const hipError_t e = smvp::launch_csr_stream_owner_repeat(h->vpt, owner_flavor(h), l, reps, grid, ctl_words,
                                                               first_of_run, patience, (hipStream_t)stream);
     if (e != hipSuccess)
         return smvp::fail(SMVP_ERR_HIP, "repeating CSR launch failed: %s", hipGetErrorString(e));
@@ -942,13 +931,12 @@ static int csr_spmv_repeat(smvp_csr_t *h, const double *d_x, double *d_y, void *
 }
 
 // stamps: device-side timing slots of this launch (owner kernel only), or nullptr
-static int csr_spmv_impl(smvp_csr_t *h, const double *d_x, double *d_y, void *stream, unsigned long long *stamps)
+int smvp::csr_spmv_stamped(smvp_csr_t *h, const double *d_x, double *d_y, void *stream, unsigned long long *stamps)
 {
     if (!h || (h->rows > 0 && !d_y) || (h->nnz > 0 && !d_x))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmv: bad argument");
-    if ((h->kernel == SMVP_CSR_KERNEL_COLSWEEP && !h->d_sweep_ptr) || (h->kernel == SMVP_CSR_KERNEL_BINNED && !h->near && !h->bin.nw.on) ||
-        (h->kernel != SMVP_CSR_KERNEL_VECTOR && h->kernel != SMVP_CSR_KERNEL_COLSWEEP && h->kernel != SMVP_CSR_KERNEL_BINNED &&
-         !h->d_tile_row))
+    if ((h->kernel == SMVP_CSR_KERNEL_COLSWEEP && !h->sweep.d_ptr) || (h->kernel == SMVP_CSR_KERNEL_BINNED && !h->binned.near && !h->binned.bin.nw.on) ||
+        (runs_on_tile_plan(h->kernel) && !h->tile.d_tile_row))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmv: the handle has no launch plan (a re-plan failed earlier)");
     DeviceScope on(h->device);
     hipStream_t st = (hipStream_t)stream;
@@ -960,61 +948,60 @@ static int csr_spmv_impl(smvp_csr_t *h, const double *d_x, double *d_y, void *st
         // 0.777 against 0.757 ms.  As one persistent workgroup per CU enqueued AHEAD of the near product the two did share
         // the CUs -- and pass A then took 264 instead of 238 us while the near product finished 241 us after it instead of
         // 303: 0.7485 against 0.7540 ms.  What one gains the other loses: profiles/r04_binned_measured.txt.)
-        if (h->bin.nw.on && h->side) {
+        if (h->binned.bin.nw.on && h->binned.side) {
             // The window plan's near part and pass A are both one-workgroup-per-CU kernels (148 / 132 KB of LDS): enqueued
             // side by side -- pass A first, on a stream of its own: it needs x only -- their workgroups share the chip one
             // CU at a time, the near part's take the CUs that pass A's last workgroups leave, and a kernel that mostly
             // reads runs beside one that writes 40 % of its bytes: 0.683-0.697 -> 0.651-0.669 ms on the random model
             // (profiles/r04_binned_measured.txt, section 12; the near part first: 0.668-0.670).  Pass B waits for both.
-            HIP_TRY(hipEventRecord(h->ev_fork, st));
-            HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-            e = smvp::launch_binned_products(h->bin, d_x, h->side);
+            HIP_TRY(hipEventRecord(h->binned.ev_fork, st));
+            HIP_TRY(hipStreamWaitEvent(h->binned.side, h->binned.ev_fork, 0));
+            e = smvp::launch_binned_products(h->binned.bin, d_x, h->binned.side);
             if (e != hipSuccess)
                 return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
             // From here on pass A is in flight on the side stream, reading x and writing the bins: whatever fails below, the
             // caller's stream is joined to it before the error goes back -- the caller may free x or destroy the handle next.
             int rc = SMVP_OK;
-            hipError_t je = hipEventRecord(h->ev_join, h->side);
+            hipError_t je = hipEventRecord(h->binned.ev_join, h->binned.side);
             if (je == hipSuccess) {
-                e = smvp::launch_near_window(h->bin.nw, d_x, d_y, st);
+                e = smvp::launch_near_window(h->binned.bin.nw, d_x, d_y, st);
                 if (e != hipSuccess)
                     rc = smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
-                je = hipStreamWaitEvent(st, h->ev_join, 0);
+                je = hipStreamWaitEvent(st, h->binned.ev_join, 0);
             }
             if (je != hipSuccess) {
-                (void)hipStreamSynchronize(h->side);  // the join could not be enqueued: wait for pass A here
+                (void)hipStreamSynchronize(h->binned.side);  // the join could not be enqueued: wait for pass A here
                 return smvp::fail(SMVP_ERR_HIP, "joining the binned plan's side stream failed: %s", hipGetErrorString(je));
             }
             if (rc != SMVP_OK)
                 return rc;
-            e = smvp::launch_binned_sums(h->bin, d_y, st);
+            e = smvp::launch_binned_sums(h->binned.bin, d_y, st);
             if (e != hipSuccess)
                 return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
             return SMVP_OK;
         }
-        if (h->bin.nw.on) {
-            e = smvp::launch_near_window(h->bin.nw, d_x, d_y, st);
+        if (h->binned.bin.nw.on) {
+            e = smvp::launch_near_window(h->binned.bin.nw, d_x, d_y, st);
             if (e != hipSuccess)
                 return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
-        } else if (int rc = csr_spmv_impl(h->near, d_x, d_y, stream, nullptr))
+        } else if (int rc = smvp::csr_spmv_stamped(h->binned.near, d_x, d_y, stream, nullptr))
             return rc;
-        e = smvp::launch_binned_products(h->bin, d_x, st);
+        e = smvp::launch_binned_products(h->binned.bin, d_x, st);
         if (e != hipSuccess)
             return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
-        e = smvp::launch_binned_sums(h->bin, d_y, st);
+        e = smvp::launch_binned_sums(h->binned.bin, d_y, st);
     } else if (h->kernel == SMVP_CSR_KERNEL_COLSWEEP)
-        e = smvp::launch_csr_colsweep(h->d_sweep_ptr, h->d_sweep_col, h->d_sweep_val, h->d_sweep_row, d_x, d_y, h->rows,
-                                      (h->sweep_parts == smvp::kSweepXcdParts ? h->sweep_rb : h->sweep_rb * h->sweep_parts) / smvp::kSweepWaves,
-                                      h->sweep_parts, h->sweep_per_launch, h->sweep_g, h->d_sweep_part, st);
+        e = smvp::launch_csr_colsweep(h->sweep.d_ptr, h->sweep.d_col, h->sweep.d_val, h->sweep.d_row, d_x, d_y, h->rows,
+                                      sweep_strip_rows(h->sweep), h->sweep.parts, h->sweep.per_launch, h->sweep.g, h->sweep.d_part, st);
     else if (h->kernel == SMVP_CSR_KERNEL_VECTOR)
         e = smvp::launch_csr_vector(h->lanes_per_row, h->d_row_ptr, h->d_col_ind, h->d_val, d_x, d_y, h->rows, st);
     else if (h->kernel == SMVP_CSR_KERNEL_STREAM) {
         smvp::OwnerLaunch l{};
         fill_owner_launch(h, d_x, d_y, stamps, &l);
-        e = smvp::launch_csr_stream_owner(h->vpt, h->d_col16 ? smvp::kFlavorCsr16 : h->flavor, l, st);
+        e = smvp::launch_csr_stream_owner(h->vpt, owner_flavor(h), l, st);
     } else
-        e = smvp::launch_csr_stream(h->vpt, h->d_row_ptr, h->d_col_ind, h->d_val, d_x, d_y, h->d_tile_row,
-                                    h->d_carry_row, h->d_carry, h->rows, h->nnz, h->ntiles, st);
+        e = smvp::launch_csr_stream(h->vpt, h->d_row_ptr, h->d_col_ind, h->d_val, d_x, d_y, h->tile.d_tile_row,
+                                    h->tile.d_carry_row, h->tile.d_carry, h->rows, h->nnz, h->tile.ntiles, st);
     if (e != hipSuccess)
         return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
     return SMVP_OK;
@@ -1022,40 +1009,43 @@ static int csr_spmv_impl(smvp_csr_t *h, const double *d_x, double *d_y, void *st
 
 extern "C" int smvp_csr_spmv(smvp_csr_t *h, const double *d_x, double *d_y, void *stream)
 {
-    return csr_spmv_impl(h, d_x, d_y, stream, nullptr);
+    return smvp::csr_spmv_stamped(h, d_x, d_y, stream, nullptr);
 }
 
-// the owner kernel of a launch small enough to be timed on the device (see StampTimer)?
-static bool csr_can_stamp(const smvp_csr_t *h) { return h && h->kernel == SMVP_CSR_KERNEL_STREAM && h->d_tile_row; }
+// the owner kernel, whose launch can time itself on the device?
+int smvp::csr_stamp_slots(const smvp_csr_t *h)
+{
+    return h && h->kernel == SMVP_CSR_KERNEL_STREAM && h->tile.d_tile_row ? smvp::owner_stamp_slots(h->tile.ntiles, h->flavor) : 0;
+}
 
 extern "C" int smvp_csr_describe(const smvp_csr_t *h, char *kernel_name, size_t cap, double *alg_bytes)
 {
     if (!h)
         return smvp::fail(SMVP_ERR_INVALID, "null handle");
     if (kernel_name && cap) {
-        if (h->kernel == SMVP_CSR_KERNEL_BINNED && h->bin.nw.on)
-            snprintf(kernel_name, cap, "csr_binned: csr_near_window + csr_binned_far_products<2> + csr_binned_far_sums<%d, %d, 2>", h->bin.slots,
-                     h->bin.threads_b);
+        if (h->kernel == SMVP_CSR_KERNEL_BINNED && h->binned.bin.nw.on)
+            snprintf(kernel_name, cap, "csr_binned: csr_near_window + csr_binned_far_products<2> + csr_binned_far_sums<%d, %d, 2>", h->binned.bin.slots,
+                     h->binned.bin.threads_b);
         else if (h->kernel == SMVP_CSR_KERNEL_BINNED)
             snprintf(kernel_name, cap, "csr_binned: csr_stream_owner<%d, %d, false> + csr_binned_far_products<2> + csr_binned_far_sums<%d, %d, 2>",
-                     h->near ? h->near->vpt : 0, h->near ? (h->near->d_col16 ? smvp::kFlavorCsr16 : h->near->flavor) : 0,
-                     h->bin.slots, h->bin.threads_b);
+                     h->binned.near ? h->binned.near->vpt : 0, h->binned.near ? owner_flavor(h->binned.near) : 0,
+                     h->binned.bin.slots, h->binned.bin.threads_b);
         else if (h->kernel == SMVP_CSR_KERNEL_COLSWEEP)
-            if (h->sweep_parts == smvp::kSweepXcdParts)
-                snprintf(kernel_name, cap, "csr_colsweep<%d> (8 column parts, one per XCD) + sweep_combine", h->sweep_g);
-            else if (h->sweep_parts > 1)
-                snprintf(kernel_name, cap, "csr_colsweep<%d> (%d column parts)", h->sweep_g, h->sweep_parts);
+            if (h->sweep.parts == smvp::kSweepXcdParts)
+                snprintf(kernel_name, cap, "csr_colsweep<%d> (8 column parts, one per XCD) + sweep_combine", h->sweep.g);
+            else if (h->sweep.parts > 1)
+                snprintf(kernel_name, cap, "csr_colsweep<%d> (%d column parts)", h->sweep.g, h->sweep.parts);
             else
-                snprintf(kernel_name, cap, "csr_colsweep<%d>", h->sweep_g);
+                snprintf(kernel_name, cap, "csr_colsweep<%d>", h->sweep.g);
         else if (h->kernel == SMVP_CSR_KERNEL_VECTOR)
             snprintf(kernel_name, cap, "csr_vector_rows<%d>", h->lanes_per_row);
         else if (h->kernel == SMVP_CSR_KERNEL_STREAM)
-            snprintf(kernel_name, cap, "csr_stream_owner<%d, %d, false>", h->vpt, h->d_col16 ? smvp::kFlavorCsr16 : h->flavor);
+            snprintf(kernel_name, cap, "csr_stream_owner<%d, %d, false>", h->vpt, owner_flavor(h));
         else
             snprintf(kernel_name, cap, "csr_stream_tiles<%d>", h->vpt);
     }
     if (alg_bytes)
-        *alg_bytes = 12.0 * h->nnz + 4.0 * (h->rows + 1.0) + 8.0 * h->cols + 8.0 * h->rows;
+        *alg_bytes = csr_matrix_bytes(h) + 8.0 * h->cols + 8.0 * h->rows;
     return SMVP_OK;
 }
 
@@ -1065,18 +1055,18 @@ extern "C" int smvp_csr_plan_launches(const smvp_csr_t *h, int *launches)
     if (!h || !launches)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_plan_launches: bad argument");
     *launches = 1;
-    if (h->kernel == SMVP_CSR_KERNEL_COLSWEEP && h->sweep_rb > 0 && h->sweep_per_launch > 0) {
-        const bool xcd = h->sweep_parts == smvp::kSweepXcdParts;
-        const int nwg = (h->rows + h->sweep_rb - 1) / h->sweep_rb * (xcd ? smvp::kSweepXcdParts : 1);
-        *launches = std::max(1, (nwg + h->sweep_per_launch - 1) / h->sweep_per_launch) + (xcd ? 1 : 0);  // (+ sweep_combine)
-    } else if (h->kernel == SMVP_CSR_KERNEL_STREAM_CARRY && h->ntiles > 1) {
+    if (h->kernel == SMVP_CSR_KERNEL_COLSWEEP && h->sweep.rb > 0 && h->sweep.per_launch > 0) {
+        const bool xcd = h->sweep.parts == smvp::kSweepXcdParts;
+        const int nwg = (h->rows + h->sweep.rb - 1) / h->sweep.rb * (xcd ? smvp::kSweepXcdParts : 1);
+        *launches = std::max(1, (nwg + h->sweep.per_launch - 1) / h->sweep.per_launch) + (xcd ? 1 : 0);  // (+ sweep_combine)
+    } else if (h->kernel == SMVP_CSR_KERNEL_STREAM_CARRY && h->tile.ntiles > 1) {
         *launches = 2;
-    } else if (h->kernel == SMVP_CSR_KERNEL_BINNED && h->bin.nw.on) {
-        *launches = 1 + (h->bin.nw.n_out > 0 ? 1 : 0) + (h->bin.nf > 0 ? 2 : 0);
-    } else if (h->kernel == SMVP_CSR_KERNEL_BINNED && h->near) {
+    } else if (h->kernel == SMVP_CSR_KERNEL_BINNED && h->binned.bin.nw.on) {
+        *launches = 1 + (h->binned.bin.nw.n_out > 0 ? 1 : 0) + (h->binned.bin.nf > 0 ? 2 : 0);
+    } else if (h->kernel == SMVP_CSR_KERNEL_BINNED && h->binned.near) {
         int near = 1;
-        (void)smvp_csr_plan_launches(h->near, &near);
-        *launches = near + (h->bin.nf > 0 ? 2 : 0);
+        (void)smvp_csr_plan_launches(h->binned.near, &near);
+        *launches = near + (h->binned.bin.nf > 0 ? 2 : 0);
     }
     return SMVP_OK;
 }
@@ -1084,26 +1074,26 @@ extern "C" int smvp_csr_plan_launches(const smvp_csr_t *h, int *launches)
 // bytes of device memory the current launch plan keeps beside row_ptr / col_ind / val
 static double csr_plan_bytes(const smvp_csr_t *h)
 {
-    const double n = h->nnz, t = h->ntiles;
+    const double n = h->nnz, t = h->tile.ntiles;
     if (h->kernel == SMVP_CSR_KERNEL_BINNED)
-        return (double)h->bin.plan_bytes + (h->near ? csr_plan_bytes(h->near) : 0.0);
+        return (double)h->binned.bin.plan_bytes + (h->binned.near ? csr_plan_bytes(h->binned.near) : 0.0);
     if (h->kernel == SMVP_CSR_KERNEL_COLSWEEP) {
-        const bool xcd = h->sweep_parts == smvp::kSweepXcdParts;
-        const int strip_rows = std::max(1, (xcd ? h->sweep_rb : h->sweep_rb * h->sweep_parts) / smvp::kSweepWaves);
-        return 14.0 * n + 8.0 * ((double)((h->rows + strip_rows - 1) / strip_rows) * h->sweep_parts + 2) + (xcd ? 64.0 * h->rows : 0.0);
+        const bool xcd = h->sweep.parts == smvp::kSweepXcdParts;
+        const int strip_rows = std::max(1, sweep_strip_rows(h->sweep));
+        return 14.0 * n + 8.0 * ((double)((h->rows + strip_rows - 1) / strip_rows) * h->sweep.parts + 2) + (xcd ? 64.0 * h->rows : 0.0);
     }
     if (h->kernel == SMVP_CSR_KERNEL_VECTOR)
         return 0.0;
     double b = 4.0 * (t + 1) + 4.0 * t;  // tile_row + tile_next (or carry_row)
     if (h->kernel == SMVP_CSR_KERNEL_STREAM_CARRY)
         b += 8.0 * t;
-    if (h->d_col16)
+    if (h->tile.d_col16)
         b += 2.0 * n + 4.0 * (n / 1024 + 1);
-    if (h->d_row_rel)
+    if (h->tile.d_row_rel)
         b += 2.0 * h->rows;
-    if (h->flavor == smvp::kFlavorTjdsS || h->flavor == smvp::kFlavorTjdsH) {
-        b += 4.0 * (t + 1) + 12.0 * h->ovf_total + 4.0 * (t + 2) + 8.0 * h->cached_total;
-        b += h->flavor == smvp::kFlavorTjdsH ? 4.0 * n + 4.0 * (t + 2) + 8.0 * h->runs_total + 2.0 * (n / 32 + 1) : 8.0 * n;
+    if (tile_ordered(h->flavor)) {
+        b += 4.0 * (t + 1) + 12.0 * h->tile.ovf_total + 4.0 * (t + 2) + 8.0 * h->tile.cached_total;
+        b += h->flavor == smvp::kFlavorTjdsH ? 4.0 * n + 4.0 * (t + 2) + 8.0 * h->tile.runs_total + 2.0 * (n / 32 + 1) : 8.0 * n;
     }
     return b;
 }
@@ -1112,7 +1102,7 @@ extern "C" int smvp_csr_plan_info(const smvp_csr_t *h, smvp_plan_info_t *out)
 {
     if (!h || !out)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_plan_info: bad argument");
-    out->matrix_bytes = 12.0 * h->nnz + 4.0 * (h->rows + 1.0);
+    out->matrix_bytes = csr_matrix_bytes(h);
     out->plan_bytes = csr_plan_bytes(h);
     out->build_ms = h->plan_build_ms;
     return SMVP_OK;
@@ -1129,31 +1119,25 @@ extern "C" int smvp_csr_spmm(smvp_csr_t *h, int k, const double *d_X, long long 
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: k = %d, ldx = %lld, ldy = %lld (need k >= 1, ldx >= k, ldy >= k)", k, ldx, ldy);
     if ((h->nnz > 0 && !d_X) || (h->rows > 0 && !d_Y))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: null %s", h->rows > 0 && !d_Y ? "d_Y" : "d_X");
-    // the byte ranges the operands span: X(c, v) for c < cols, Y(r, v) for r < rows (v < k)
-    const unsigned __int128 xa = (uintptr_t)d_X, ya = (uintptr_t)d_Y;
-    const unsigned __int128 xb = xa + ((unsigned __int128)(h->cols > 0 ? h->cols - 1 : 0) * (unsigned long long)ldx + (unsigned)k) * 8u;
-    const unsigned __int128 yb = ya + ((unsigned __int128)(h->rows > 0 ? h->rows - 1 : 0) * (unsigned long long)ldy + (unsigned)k) * 8u;
-    if (d_X && d_Y && h->cols > 0 && h->rows > 0 && xa < yb && ya < xb)
+    if (operands_overlap(d_X, ldx, h->cols, d_Y, ldy, h->rows, k))  // X(c, v) for c < cols, Y(r, v) for r < rows (v < k)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: the byte ranges of d_X and d_Y overlap");
     DeviceScope on(h->device);
     hipStream_t st = (hipStream_t)stream;
-    if (!h->spmm_planned) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIP_TRY(hipStreamIsCapturing(st, &cs));
-        if (cs != hipStreamCaptureStatusNone)
-            return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: the first call on a handle builds its plan and cannot be captured "
-                                                "(call it once outside the capture)");
-        const double t0 = wall_ms();
-        if (h->rows > 0 && !h->d_spmm_order && hipMalloc((void **)&h->d_spmm_order, sizeof(int) * (size_t)h->rows) != hipSuccess) {
-            h->d_spmm_order = nullptr;
-            return smvp::fail(SMVP_ERR_ALLOC, "smvp_csr_spmm: cannot allocate the plan (%d rows)", h->rows);
-        }
-        if (int rc = smvp::build_spmm_order(h->d_row_ptr, h->rows, h->max_row_len, h->d_spmm_order, st))
+    if (!h->spmm.planned) {
+        if (int rc = refuse_capture(st, "smvp_csr_spmm: the first call on a handle builds its plan and cannot be captured "
+                                        "(call it once outside the capture)"))
             return rc;
-        h->spmm_planned = true;
-        h->spmm_build_ms = wall_ms() - t0;
+        const double t0 = wall_ms();
+        int *order = h->spmm.d_order;  // (kept from a call whose build failed)
+        if (h->rows > 0 && !order && hipMalloc((void **)&order, sizeof(int) * (size_t)h->rows) != hipSuccess)
+            return smvp::fail(SMVP_ERR_ALLOC, "smvp_csr_spmm: cannot allocate the plan (%d rows)", h->rows);
+        h->spmm.d_order = order;
+        if (int rc = smvp::build_spmm_order(h->d_row_ptr, h->rows, h->max_row_len, h->spmm.d_order, st))
+            return rc;
+        h->spmm.planned = true;
+        h->spmm.build_ms = wall_ms() - t0;
     }
-    const hipError_t e = smvp::launch_csr_spmm(h->d_row_ptr, h->d_col_ind, h->d_val, h->d_spmm_order, d_X, ldx, d_Y, ldy, h->rows, k, st);
+    const hipError_t e = smvp::launch_csr_spmm(h->d_row_ptr, h->d_col_ind, h->d_val, h->spmm.d_order, d_X, ldx, d_Y, ldy, h->rows, k, st);
     if (e != hipSuccess)
         return smvp::fail(SMVP_ERR_HIP, "smvp_csr_spmm: launch failed: %s", hipGetErrorString(e));
     return SMVP_OK;
@@ -1170,11 +1154,11 @@ extern "C" int smvp_csr_spmm_describe(const smvp_csr_t *h, int k, char *kernel_n
     if (kernel_name && cap)
         smvp::spmm_kernel_name(k, kernel_name, cap);
     if (alg_bytes)
-        *alg_bytes = 12.0 * h->nnz + 4.0 * (h->rows + 1.0) + 8.0 * k * ((double)h->cols + h->rows);
+        *alg_bytes = csr_matrix_bytes(h) + 8.0 * k * ((double)h->cols + h->rows);
     if (plan) {
-        plan->matrix_bytes = 12.0 * h->nnz + 4.0 * (h->rows + 1.0);
-        plan->plan_bytes = h->spmm_planned ? 4.0 * h->rows : 0.0;
-        plan->build_ms = h->spmm_planned ? h->spmm_build_ms : 0.0;
+        plan->matrix_bytes = csr_matrix_bytes(h);
+        plan->plan_bytes = h->spmm.planned ? 4.0 * h->rows : 0.0;
+        plan->build_ms = h->spmm.planned ? h->spmm.build_ms : 0.0;
     }
     return SMVP_OK;
 }
@@ -1206,11 +1190,9 @@ extern "C" int smvp_csr_create_transposed(smvp_csr_t **out, const smvp_csr_t *h,
         return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_create_transposed: plain CSR handles only (this one belongs to a TJDS matrix)");
     DeviceScope on(h->device);
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(st, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_create_transposed: allocates and synchronises, so it cannot be captured "
-                                            "(the stream is capturing)");
+    if (int rc = refuse_capture(st, "smvp_csr_create_transposed: allocates and synchronises, so it cannot be captured "
+                                    "(the stream is capturing)"))
+        return rc;
     const int t_rows = h->cols, t_cols = h->rows, nnz = h->nnz;
     int *t_row_ptr = nullptr, *t_col_ind = nullptr;
     double *t_val = nullptr;
@@ -1262,11 +1244,10 @@ extern "C" void smvp_csr_destroy(smvp_csr_t *h)
     DeviceScope on(h->device);
     smvp::debug_owner_phases();  // (print in diagnostic builds only)
     smvp::debug_binned_phases();
-    free_stream_plan(h);
-    free_sweep_plan(h);
-    free_binned(h);
-    if (h->d_spmm_order)
-        (void)hipFree(h->d_spmm_order);
+    free_tile_plan(&h->tile);
+    free_sweep_plan(&h->sweep);
+    free_binned_side(&h->binned);
+    free_spmm_plan(&h->spmm);
     if (h->own_row_ptr && h->d_row_ptr)
         (void)hipFree(h->d_row_ptr);
     if (h->own_col_ind && h->d_col_ind)
@@ -1564,7 +1545,7 @@ extern "C" int smvp_tjds_zero_y(smvp_tjds_t *h, double *d_y, void *stream)
     return SMVP_OK;
 }
 
-static int tjds_spmv_impl(smvp_tjds_t *h, double *d_y, void *stream, unsigned long long *stamps)
+int smvp::tjds_spmv_stamped(smvp_tjds_t *h, double *d_y, void *stream, unsigned long long *stamps)
 {
     if (!h || (h->rows > 0 && !d_y))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv: bad argument");
@@ -1574,7 +1555,7 @@ static int tjds_spmv_impl(smvp_tjds_t *h, double *d_y, void *stream, unsigned lo
         return smvp::fail(SMVP_ERR_UNSUPPORTED, "ref-quirks mode indexes the operand by row and needs a square matrix");
     DeviceScope on(h->device);
     if (!h->quirks && h->mode == SMVP_TJDS_MODE_ROW_GATHER)
-        return csr_spmv_impl(h->rg, h->d_x_perm, d_y, stream, stamps);
+        return smvp::csr_spmv_stamped(h->rg, h->d_x_perm, d_y, stream, stamps);
     if (h->mode == SMVP_TJDS_MODE_TWO_PHASE && !h->quirks) {
         hipError_t e1 = smvp::launch_tjds_products(h->d_plan_start_pos, h->d_val, h->d_x_perm, h->d_prod, h->d_work,
                                                    h->nwork, h->cols, (hipStream_t)stream);
@@ -1591,12 +1572,21 @@ static int tjds_spmv_impl(smvp_tjds_t *h, double *d_y, void *stream, unsigned lo
 
 extern "C" int smvp_tjds_spmv(smvp_tjds_t *h, double *d_y, void *stream)
 {
-    return tjds_spmv_impl(h, d_y, stream, nullptr);
+    return smvp::tjds_spmv_stamped(h, d_y, stream, nullptr);
 }
 
-static bool tjds_can_stamp(const smvp_tjds_t *h)
+// the row-gather product (which overwrites y) through the owner kernel of `rg`, on the operand of smvp_tjds_set_x
+int smvp::tjds_stamp_slots(const smvp_tjds_t *h)
 {
-    return h && !h->quirks && h->mode == SMVP_TJDS_MODE_ROW_GATHER && csr_can_stamp(h->rg);
+    return h && !h->quirks && h->mode == SMVP_TJDS_MODE_ROW_GATHER ? smvp::csr_stamp_slots(h->rg) : 0;
+}
+
+int smvp::tjds_repeat_grid(const smvp_tjds_t *h) { return smvp::csr_repeat_grid(h->rg); }
+
+int smvp::tjds_spmv_repeat(smvp_tjds_t *h, double *d_y, void *stream, unsigned long long *stamps, int reps, int grid, unsigned *ctl_words,
+                           bool first_of_run, unsigned long long patience)
+{
+    return smvp::csr_spmv_repeat(h->rg, h->d_x_perm, d_y, stream, stamps, reps, grid, ctl_words, first_of_run, patience);
 }
 
 extern "C" int smvp_tjds_set_ref_quirks(smvp_tjds_t *h, int enable, int ref_num_tjdiag, int last_diag_single)
@@ -1633,10 +1623,7 @@ extern "C" int smvp_tjds_spmv_transposed(smvp_tjds_t *h, const double *d_x, doub
         return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv_transposed: null handle");
     if ((h->nnz > 0 && !d_x) || (h->cols > 0 && !d_y))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv_transposed: null %s", h->cols > 0 && !d_y ? "d_y" : "d_x");
-    // the byte ranges the operands span: x[0 .. rows), y[0 .. cols)
-    const unsigned __int128 xa = (uintptr_t)d_x, ya = (uintptr_t)d_y;
-    const unsigned __int128 xb = xa + (unsigned __int128)(unsigned)h->rows * 8u, yb = ya + (unsigned __int128)(unsigned)h->cols * 8u;
-    if (d_x && d_y && h->rows > 0 && h->cols > 0 && xa < yb && ya < xb)
+    if (operands_overlap(d_x, 1, h->rows, d_y, 1, h->cols, 1))  // x[0 .. rows), y[0 .. cols)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv_transposed: the byte ranges of d_x and d_y overlap");
     DeviceScope on(h->device);
     const hipError_t e = smvp::launch_tjds_transposed(h->d_start_pos, h->d_row_ind, h->d_val, h->d_perm, d_x, d_y, h->cols,
@@ -1668,11 +1655,7 @@ extern "C" int smvp_tjds_spmm_transposed(smvp_tjds_t *h, int k, const double *d_
                           ldx, ldy);
     if ((h->nnz > 0 && !d_X) || (h->cols > 0 && !d_Y))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: null %s", h->cols > 0 && !d_Y ? "d_Y" : "d_X");
-    // the byte ranges the operands span: X(r, v) for r < rows, Y(c, v) for c < cols (v < k)
-    const unsigned __int128 xa = (uintptr_t)d_X, ya = (uintptr_t)d_Y;
-    const unsigned __int128 xb = xa + ((unsigned __int128)(h->rows > 0 ? h->rows - 1 : 0) * (unsigned long long)ldx + (unsigned)k) * 8u;
-    const unsigned __int128 yb = ya + ((unsigned __int128)(h->cols > 0 ? h->cols - 1 : 0) * (unsigned long long)ldy + (unsigned)k) * 8u;
-    if (d_X && d_Y && h->rows > 0 && h->cols > 0 && xa < yb && ya < xb)
+    if (operands_overlap(d_X, ldx, h->rows, d_Y, ldy, h->cols, k))  // X(r, v) for r < rows, Y(c, v) for c < cols (v < k)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: the byte ranges of d_X and d_Y overlap");
     DeviceScope on(h->device);
     const hipError_t e = smvp::launch_tjds_spmm_transposed(h->d_start_pos, h->d_row_ind, h->d_val, h->d_perm, d_X, ldx, d_Y, ldy,
@@ -1701,23 +1684,23 @@ extern "C" int smvp_tjds_set_value_cache(smvp_tjds_t *h, int min_tiles)
 {
     if (!h || !h->rg || min_tiles < 0 || min_tiles > 16)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_set_value_cache: needs the row-gather plan and 0 <= min_tiles <= 16");
-    if (h->rg->flavor != smvp::kFlavorTjdsS && h->rg->flavor != smvp::kFlavorTjdsH)
+    if (!tile_ordered(h->rg->flavor))
         return min_tiles == 0 ? (int)SMVP_OK
                               : smvp::fail(SMVP_ERR_UNSUPPORTED, "the value cache belongs to the tile-ordered TJDS stream");
     DeviceScope on(h->device);
     h->rg->cache_min_tiles = min_tiles;
-    return build_stream_plan(h->rg);
+    return build_tile_plan(h->rg);
 }
 
 extern "C" int smvp_tjds_get_value_cache(const smvp_tjds_t *h, int *min_tiles, long long *cached_entries)
 {
     if (!h)
         return smvp::fail(SMVP_ERR_INVALID, "null handle");
-    const bool on = h->rg && (h->rg->flavor == smvp::kFlavorTjdsS || h->rg->flavor == smvp::kFlavorTjdsH);
+    const bool on = h->rg && tile_ordered(h->rg->flavor);
     if (min_tiles)
         *min_tiles = on ? h->rg->cache_min_tiles : 0;
     if (cached_entries)
-        *cached_entries = on ? h->rg->cached_total : 0;
+        *cached_entries = on ? h->rg->tile.cached_total : 0;
     return SMVP_OK;
 }
 
@@ -1773,564 +1756,3 @@ extern "C" void smvp_tjds_destroy(smvp_tjds_t *h)
     delete h;
 }
 
-// ===========================================================================
-// device queries
-// ===========================================================================
-extern "C" int smvp_device_count(int *count)
-{
-    if (!count)
-        return smvp::fail(SMVP_ERR_INVALID, "null argument");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess)
-        n = 0;
-    *count = n;
-    return SMVP_OK;
-}
-
-extern "C" int smvp_device_info(int device, char *name, size_t name_cap, int *compute_units, size_t *hbm_bytes)
-{
-    if (int rc = usable_device(device))
-        return rc;
-    hipDeviceProp_t p;
-    HIP_TRY(hipGetDeviceProperties(&p, device));
-    if (name && name_cap) {
-        if (p.name[0])
-            snprintf(name, name_cap, "%s (%s)", p.name, p.gcnArchName);
-        else  // some driver stacks leave the marketing name empty
-            snprintf(name, name_cap, "%s", p.gcnArchName);
-    }
-    if (compute_units)
-        *compute_units = p.multiProcessorCount;
-    if (hbm_bytes)
-        *hbm_bytes = p.totalGlobalMem;
-    return SMVP_OK;
-}
-
-// ===========================================================================
-// reference-shaped entry points
-// ===========================================================================
-extern "C" void smvp_run_opts_default(smvp_run_opts_t *o)
-{
-    if (!o)
-        return;
-    memset(o, 0, sizeof *o);
-    o->struct_size = (unsigned)sizeof *o;
-    o->shard_exchange = SMVP_EXCHANGE_AUTO;
-    o->csr_kernel = SMVP_CSR_KERNEL_AUTO;
-    o->tjds_mode = SMVP_TJDS_MODE_AUTO;
-    o->timing = SMVP_TIMING_AUTO;
-}
-
-namespace {
-
-constexpr int kEventRing = 1024;
-
-// Scope guard for the scratch the two entry points allocate.
-struct RunScratch {
-    std::vector<double> ms;   // per-product times, filled as the event ring is drained
-    double *d_x = nullptr, *d_y = nullptr;
-    double *d_result = nullptr;                          // where the last product was written (d_x or d_y when iterating)
-    unsigned long long *d_norm = nullptr;                // scratch of the normalisation
-    void *d_coo = nullptr;                               // convert_on_device: the uploaded COO
-    int *d_i0 = nullptr, *d_i1 = nullptr, *d_i2 = nullptr;  // ... and the arrays built from it
-    double *d_v = nullptr;
-    std::vector<hipEvent_t> ev;
-    hipStream_t stream = nullptr;
-    smvp_csr_t *csr = nullptr;
-    smvp_tjds_t *tjds = nullptr;
-    ~RunScratch()
-    {
-        for (hipEvent_t e : ev)
-            (void)hipEventDestroy(e);
-        if (d_norm)
-            (void)hipFree(d_norm);
-        if (d_x)
-            (void)hipFree(d_x);
-        if (d_y)
-            (void)hipFree(d_y);
-        if (stream)
-            (void)hipStreamDestroy(stream);
-        smvp_csr_destroy(csr);
-        smvp_tjds_destroy(tjds);
-        for (void *p : {d_coo, (void *)d_i0, (void *)d_i1, (void *)d_i2, (void *)d_v})
-            if (p)
-                (void)hipFree(p);
-    }
-};
-
-int prepare_run(RunScratch &s, int rows, int cols, int iters, const smvp_run_opts_t *o)
-{
-    HIP_TRY(hipStreamCreate(&s.stream));
-    HIP_TRY(hipMalloc((void **)&s.d_x, sizeof(double) * (size_t)std::max(std::max(cols, rows), 1)));
-    HIP_TRY(hipMalloc((void **)&s.d_y, sizeof(double) * (size_t)std::max(std::max(cols, rows), 1)));
-    HIP_TRY(hipMalloc((void **)&s.d_norm, sizeof(unsigned long long)));
-    s.d_result = s.d_y;
-    if (o->x) {
-        HIP_TRY(hipMemcpy(s.d_x, o->x, sizeof(double) * (size_t)cols, hipMemcpyHostToDevice));
-    } else {
-        // vectorInit(rows, onesVector, 1), main-cli.c:368-369 / :761-762
-        hipError_t e = smvp::launch_fill(s.d_x, 1.0, std::max(cols, rows), s.stream);
-        if (e != hipSuccess)
-            return smvp::fail(SMVP_ERR_HIP, "fill launch failed: %s", hipGetErrorString(e));
-    }
-    // a ring of event pairs, drained every kEventRing products: -n may be in the millions
-    s.ev.assign((size_t)std::min(iters, kEventRing) * 2, nullptr);
-    for (auto &e : s.ev)
-        HIP_TRY(hipEventCreate(&e));
-    s.ms.assign((size_t)iters, 0.0);
-    return SMVP_OK;
-}
-
-// events of product i
-inline hipEvent_t &ev_start(RunScratch &s, int i) { return s.ev[(size_t)2 * (i % kEventRing)]; }
-inline hipEvent_t &ev_stop(RunScratch &s, int i) { return s.ev[(size_t)2 * (i % kEventRing) + 1]; }
-
-// after product i has been enqueued: when the ring is full (or i is the last product) wait and read it out
-int drain_ring(RunScratch &s, int i, int iters)
-{
-    if ((i + 1) % kEventRing != 0 && i + 1 != iters)
-        return SMVP_OK;
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    for (int k = i - (i % kEventRing); k <= i; ++k) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev_start(s, k), ev_stop(s, k)));
-        s.ms[(size_t)k] = (double)ms;
-    }
-    return SMVP_OK;
-}
-
-int finish_run(RunScratch &s, int rows, int iters, double *y, double *time_each_ms, smvp_time_stats_t *stats)
-{
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    if (time_each_ms)
-        memcpy(time_each_ms, s.ms.data(), sizeof(double) * (size_t)iters);
-    if (stats)
-        smvp_time_stats(s.ms.data(), iters, stats);
-    if (rows > 0)
-        HIP_TRY(hipMemcpy(y, s.d_result, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost));
-    return SMVP_OK;
-}
-
-int check_iterate(const smvp_run_opts_t *o, int rows, int cols)
-{
-    if (o->struct_size != (unsigned)sizeof(smvp_run_opts_t))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_run_opts_t of %u bytes, this library's has %u: initialise it with "
-                                            "smvp_run_opts_default and build against this library's header",
-                          o->struct_size, (unsigned)sizeof(smvp_run_opts_t));
-    if (o->iterate && rows != cols)
-        return smvp::fail(SMVP_ERR_INVALID, "power iteration needs a square matrix (%d x %d given)", rows, cols);
-    if (o->timing < SMVP_TIMING_AUTO || o->timing > SMVP_TIMING_DEVICE_GRAPH)
-        return smvp::fail(SMVP_ERR_INVALID, "unknown timing method %d", o->timing);
-    return SMVP_OK;
-}
-
-thread_local smvp_run_info_t g_last_run = {SMVP_TIMING_EVENTS, 0, 0.0, 0.0, 0, 0};
-
-double host_ms()
-{
-    timespec t;
-    clock_gettime(CLOCK_MONOTONIC_RAW, &t);  // the reference's clock, main-cli.c:408
-    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
-}
-
-// Per-product times of launches too short for an event pair to time.  The reference brackets its product with
-// clock_gettime (main-cli.c:408-419): nothing but the product is inside the window.  A hipEvent pair around a launch
-// of a few microseconds measures mostly the events themselves (an empty launch between two events reads 6.6 us on
-// MI355X, memplus.mtx's CSR kernel runs 3.8 us), so for such launches the kernel times itself: every wave writes the
-// constant-rate wall clock when it starts and when its last store has been acknowledged, stamp_reduce takes
-// max(last) - min(first) per product.  The products of a run are captured into one hipGraph (kStampRing products per
-// replay, their timing slots baked into the nodes) so that the host's launch rate is not what the run waits for.
-constexpr int kStampRing = 256;        // products per graph replay (even: power iteration swaps x and y)
-constexpr int kStampMaxSlots = 16384;  // waves per launch up to which the kernel times itself (4096 workgroups)
-
-struct StampTimer {
-    unsigned long long *d_stamps = nullptr, *d_first_last = nullptr;
-    unsigned *d_ctl = nullptr;  // the repeating launch's barrier counters
-    hipGraphExec_t exec = nullptr;
-    int exec_n = 0;
-    ~StampTimer()
-    {
-        if (exec)
-            (void)hipGraphExecDestroy(exec);
-        if (d_stamps)
-            (void)hipFree(d_stamps);
-        if (d_first_last)
-            (void)hipFree(d_first_last);
-        if (d_ctl)
-            (void)hipFree(d_ctl);
-    }
-};
-
-// `iters` products on s.stream, each timed on its own.  pre(y): work the reference keeps outside its window (clearing
-// y); product(x, y, stamps): the launches of one product.  stamp_slots > 0: the product can time itself on the device.
-// repeat_grid > 0: the product has a repeating form -- repeat(x, y, stamps, reps, grid, ctl_words) enqueues `reps` products as
-// ONE launch that stamps every product's window (needs no `pre`); used for device-timed runs unless SMVP_TIMING_DEVICE_GRAPH asks
-// for one launch per product.
-template <class Pre, class Product, class Repeat>
-int run_timed_products(RunScratch &s, int rows, int iters, const smvp_run_opts_t *o, int stamp_slots, Pre pre, Product product,
-                       int repeat_grid, Repeat repeat)
-{
-    double *xc = s.d_x, *yc = s.d_y;
-    const bool device_asked = o->timing == SMVP_TIMING_DEVICE || o->timing == SMVP_TIMING_DEVICE_GRAPH;
-    const bool stamped = o->timing != SMVP_TIMING_EVENTS && !o->iterate && stamp_slots > 0 && (device_asked || stamp_slots <= kStampMaxSlots);
-    if (device_asked && !stamped)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "device-side timing needs the tile kernel of one GPU and no --iterate");
-    g_last_run.timing = stamped ? SMVP_TIMING_DEVICE : SMVP_TIMING_EVENTS;
-    g_last_run.graph_replays = 0;
-    g_last_run.repeat_launches = 0;
-    g_last_run.repeat_gave_up = 0;
-    const unsigned long long patience = smvp::repeat_patience_ticks(o->repeat_patience_us);
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    const double t0 = host_ms();
-    bool repeated = false;
-    int khz = 0;
-    if (stamped) {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-        if (khz <= 0)
-            return smvp::fail(SMVP_ERR_HIP, "the device reports no wall-clock rate");
-        g_last_run.device_clock_khz = khz;
-    }
-    if (stamped && repeat_grid > 0 && o->timing != SMVP_TIMING_DEVICE_GRAPH) {
-        // Up to kRepeatRing products per launch of the repeating kernel, the launches of a run enqueued one behind the other:
-        // every launch's windows are reduced on the device into first_last[product] and its give-up word is set aside; the
-        // host waits once per kRepeatSuper products -- and once for the FIRST launch of the run, before it queues any other.  A
-        // launch that gave up at one of its barriers (the grid was not resident as a whole: another stream, thread or process on
-        // the device -- the occupancy query the grid was sized from knows nothing of those) sends the whole run to the single
-        // launches below: it has waited `repeat_patience_us` (50 ms) at most, and launches queued behind it read the run's
-        // sticky give-up word and leave as they start.
-        constexpr int kRepeatRing = 1024, kRepeatSuper = 1 << 20;
-        StampTimer st;
-        unsigned *d_tops = nullptr;
-        const int slots = repeat_grid * (smvp::kStreamBlock / 64);
-        const size_t per_product = (size_t)slots * 2;
-        int ring = std::min(iters, kRepeatRing);
-        while (ring > 64 && sizeof(unsigned long long) * per_product * (size_t)ring > (64u << 20))
-            ring /= 2;  // (stamps of one launch: at most 64 MB)
-        const int super = std::min(iters, kRepeatSuper), launches_per_super = (super + ring - 1) / ring;
-        HIP_TRY(hipMalloc((void **)&st.d_stamps, sizeof(unsigned long long) * per_product * (size_t)ring));
-        HIP_TRY(hipMalloc((void **)&st.d_first_last, sizeof(unsigned long long) * 2 * (size_t)super + sizeof(unsigned) * (size_t)launches_per_super));
-        HIP_TRY(hipMalloc((void **)&st.d_ctl, sizeof(unsigned) * smvp::kRepeatCtlWords));
-        d_tops = reinterpret_cast<unsigned *>(st.d_first_last + 2 * (size_t)super);
-        std::vector<unsigned long long> fl((size_t)super * 2);
-        std::vector<unsigned> tops((size_t)launches_per_super);
-        repeated = true;
-        for (int s0 = 0; s0 < iters && repeated; s0 += super) {
-            const int ns = std::min(super, iters - s0);
-            int launches = 0;
-            for (int i0 = 0; i0 < ns; i0 += ring, ++launches) {
-                const int n = std::min(ring, ns - i0);
-                const bool first_of_run = s0 == 0 && i0 == 0;
-                if (int rc = repeat(xc, yc, st.d_stamps, n, repeat_grid, st.d_ctl, first_of_run, patience))
-                    return rc;
-                HIP_TRY(smvp::launch_stamp_reduce(st.d_stamps, slots, n, st.d_first_last + 2 * (size_t)i0, s.stream));
-                HIP_TRY(hipMemcpyAsync(d_tops + launches, st.d_ctl + smvp::kRepeatCtlWords - 32, sizeof(unsigned), hipMemcpyDeviceToDevice, s.stream));
-                if (first_of_run && ns > n) {  // more launches would follow: has this one held?
-                    HIP_TRY(hipMemcpyAsync(tops.data(), d_tops, sizeof(unsigned), hipMemcpyDeviceToHost, s.stream));
-                    HIP_TRY(hipStreamSynchronize(s.stream));
-                    if (tops[0] & 0x80000000u) {
-                        repeated = false;
-                        break;
-                    }
-                }
-            }
-            if (!repeated)
-                break;
-            HIP_TRY(hipMemcpyAsync(fl.data(), st.d_first_last, sizeof(unsigned long long) * 2 * (size_t)ns, hipMemcpyDeviceToHost, s.stream));
-            HIP_TRY(hipMemcpyAsync(tops.data(), d_tops, sizeof(unsigned) * (size_t)launches, hipMemcpyDeviceToHost, s.stream));
-            HIP_TRY(hipStreamSynchronize(s.stream));
-            for (int l = 0; l < launches; ++l)
-                if (tops[(size_t)l] & 0x80000000u)
-                    repeated = false;  // gave up at a barrier: nothing of this run is trusted
-            if (!repeated)
-                break;
-            g_last_run.repeat_launches += launches;
-            for (int k = 0; k < ns; ++k)
-                s.ms[(size_t)(s0 + k)] = (double)(fl[2 * (size_t)k + 1] - fl[2 * (size_t)k]) / (double)khz;
-        }
-        if (!repeated) {
-            g_last_run.repeat_launches = 0;
-            g_last_run.repeat_gave_up = 1;
-        }
-        s.d_result = yc;
-    }
-    if (stamped && !repeated) {
-        StampTimer st;
-        const size_t per_product = (size_t)stamp_slots * 2;
-        const int ring = std::min(iters, kStampRing);
-        HIP_TRY(hipMalloc((void **)&st.d_stamps, sizeof(unsigned long long) * per_product * (size_t)ring));
-        HIP_TRY(hipMalloc((void **)&st.d_first_last, sizeof(unsigned long long) * 2 * (size_t)ring));
-        std::vector<unsigned long long> fl((size_t)ring * 2);
-        bool use_graph = true;
-        for (int i0 = 0; i0 < iters; i0 += ring) {
-            const int n = std::min(ring, iters - i0);
-            auto enqueue = [&]() -> int {
-                for (int k = 0; k < n; ++k) {
-                    if (int rc = pre(yc))
-                        return rc;
-                    if (int rc = product(xc, yc, st.d_stamps + per_product * (size_t)k))
-                        return rc;
-                }
-                return SMVP_OK;
-            };
-            if (use_graph && st.exec_n != n) {
-                if (st.exec)
-                    (void)hipGraphExecDestroy(st.exec);
-                st.exec = nullptr;
-                st.exec_n = 0;
-                hipGraph_t graph = nullptr;
-                bool ok = hipStreamBeginCapture(s.stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                int rc = ok ? enqueue() : SMVP_OK;
-                if (ok)
-                    ok = hipStreamEndCapture(s.stream, &graph) == hipSuccess && graph && rc == SMVP_OK;
-                if (ok)
-                    ok = hipGraphInstantiate(&st.exec, graph, nullptr, nullptr, 0) == hipSuccess;
-                if (graph)
-                    (void)hipGraphDestroy(graph);
-                if (rc != SMVP_OK)
-                    return rc;
-                if (!ok) {  // no graph support for this sequence: plain launches, still timed on the device
-                    (void)hipGetLastError();
-                    st.exec = nullptr;
-                    use_graph = false;
-                } else {
-                    st.exec_n = n;
-                }
-            }
-            if (use_graph) {
-                HIP_TRY(hipGraphLaunch(st.exec, s.stream));
-                ++g_last_run.graph_replays;
-            } else if (int rc = enqueue()) {
-                return rc;
-            }
-            HIP_TRY(smvp::launch_stamp_reduce(st.d_stamps, stamp_slots, n, st.d_first_last, s.stream));
-            HIP_TRY(hipMemcpyAsync(fl.data(), st.d_first_last, sizeof(unsigned long long) * 2 * (size_t)n,
-                                   hipMemcpyDeviceToHost, s.stream));
-            HIP_TRY(hipStreamSynchronize(s.stream));
-            for (int k = 0; k < n; ++k)
-                s.ms[(size_t)(i0 + k)] = (double)(fl[2 * (size_t)k + 1] - fl[2 * (size_t)k]) / (double)khz;
-        }
-        s.d_result = yc;
-    } else if (!stamped) {
-        for (int i = 0; i < iters; ++i) {
-            if (int rc = pre(yc))
-                return rc;
-            HIP_TRY(hipEventRecord(ev_start(s, i), s.stream));
-            if (int rc = product(xc, yc, nullptr))
-                return rc;
-            HIP_TRY(hipEventRecord(ev_stop(s, i), s.stream));
-            if (o->iterate && o->normalize)  // scaling the iterate is not part of the product: outside the window,
-                HIP_TRY(smvp::launch_normalize_max(yc, rows, s.d_norm, s.stream));  // on one GPU and on several alike
-            if (int rc = drain_ring(s, i, iters))
-                return rc;
-            s.d_result = yc;
-            if (o->iterate)
-                std::swap(xc, yc);  // x_{k+1} = y_k
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    g_last_run.wall_ms = host_ms() - t0;
-    return SMVP_OK;
-}
-
-}  // namespace
-
-extern "C" int smvp_last_run_info(smvp_run_info_t *out)
-{
-    if (!out)
-        return smvp::fail(SMVP_ERR_INVALID, "null argument");
-    *out = g_last_run;
-    return SMVP_OK;
-}
-
-// opts.ngpus > 1: the same timed loop over row blocks on several GPUs; the window is the local products
-// plus the all-gather of y, the longest GPU counts (smvp_sharded.hip)
-static int sharded_compute(bool tjds, const smvp_coo_t *coo, int rows, int cols, int nnz, int iters,
-                           const smvp_run_opts_t *o, double *y, double *time_each_ms, smvp_time_stats_t *stats)
-{
-    if (o->timing == SMVP_TIMING_DEVICE || o->timing == SMVP_TIMING_DEVICE_GRAPH)  // the in-kernel stamps time one launch of one GPU; a sharded product is several
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "device-side timing is not available with more than one GPU (use events)");
-    smvp_sharded_t *h = nullptr;
-    smvp_shard_opts_t so;
-    smvp_shard_opts_default(&so);
-    so.exchange = o->shard_exchange;
-    int rc;
-    if (tjds) {
-        rc = smvp_tjds_sharded_create_ex(&h, o->ngpus, nullptr, coo, rows, cols, nnz, &so);
-    } else {
-        std::vector<int> row_ptr((size_t)rows + 1), col_ind((size_t)std::max(nnz, 1));
-        std::vector<double> val((size_t)std::max(nnz, 1));
-        rc = smvp_csr_from_coo(coo, rows, nnz, row_ptr.data(), col_ind.data(), val.data());
-        if (rc == SMVP_OK)
-            rc = smvp_csr_sharded_create_ex(&h, o->ngpus, nullptr, rows, cols, nnz, row_ptr.data(), col_ind.data(), val.data(), &so);
-    }
-    std::vector<double> local;
-    if (!time_each_ms) {
-        local.resize((size_t)iters);
-        time_each_ms = local.data();
-    }
-    if (rc == SMVP_OK && !tjds && (o->csr_kernel != SMVP_CSR_KERNEL_AUTO || o->csr_param != 0))
-        rc = smvp_sharded_set_csr_kernel(h, o->csr_kernel, o->csr_param);
-    if (rc == SMVP_OK)
-        rc = smvp_sharded_set_x(h, o->x);
-    for (int i = 0; rc == SMVP_OK && i < iters; ++i) {
-        rc = smvp_sharded_spmv(h, SMVP_GATHER_OVERLAPPED, 1);
-        if (rc == SMVP_OK)
-            rc = smvp_sharded_synchronize(h, &time_each_ms[i]);
-        if (rc == SMVP_OK && o->iterate && (i + 1 < iters || o->normalize))
-            rc = smvp_sharded_feed_back(h, o->normalize);  // the gathered y is the next operand on every GPU
-    }
-    if (rc == SMVP_OK)
-        rc = smvp_sharded_get_y(h, 0, 1, y);
-    if (rc == SMVP_OK && stats)
-        smvp_time_stats(time_each_ms, iters, stats);
-    smvp_sharded_destroy(h);
-    return rc;
-}
-
-extern "C" int smvp_csr_compute(const smvp_coo_t *coo, int rows, int cols, int nnz, int iters,
-                                const smvp_run_opts_t *opts, double *y, double *time_each_ms,
-                                smvp_time_stats_t *stats)
-{
-    smvp_run_opts_t def;
-    smvp_run_opts_default(&def);
-    const smvp_run_opts_t *o = opts ? opts : &def;
-    if (iters < 1 || rows < 0 || cols < 0 || nnz < 0 || (rows > 0 && !y))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_compute: bad argument");
-    if (int rc = check_iterate(o, rows, cols))
-        return rc;
-    if (o->ngpus > 1)
-        return sharded_compute(false, coo, rows, cols, nnz, iters, o, y, time_each_ms, stats);
-    if (int rc = usable_device(o->device))
-        return rc;
-    DeviceScope on(o->device);
-
-    RunScratch s;
-    if (o->convert_on_device) {
-        // COO goes to HBM as it is; sort + scan there; the arrays stay where they were built
-        HIP_TRY(hipMalloc(&s.d_coo, sizeof(smvp_coo_t) * (size_t)std::max(nnz, 1)));
-        HIP_TRY(hipMalloc((void **)&s.d_i0, sizeof(int) * ((size_t)rows + 1)));
-        HIP_TRY(hipMalloc((void **)&s.d_i1, sizeof(int) * (size_t)std::max(nnz, 1)));
-        HIP_TRY(hipMalloc((void **)&s.d_v, sizeof(double) * (size_t)std::max(nnz, 1)));
-        if (nnz > 0)
-            HIP_TRY(hipMemcpy(s.d_coo, coo, sizeof(smvp_coo_t) * (size_t)nnz, hipMemcpyHostToDevice));
-        if (int rc = smvp_csr_from_coo_device((const smvp_coo_t *)s.d_coo, rows, cols, nnz, s.d_i0, s.d_i1, s.d_v, nullptr))
-            return rc;
-        if (int rc = smvp_csr_create(&s.csr, o->device, rows, cols, nnz, s.d_i0, s.d_i1, s.d_v, SMVP_MEM_DEVICE, nullptr))
-            return rc;
-    } else {
-        std::vector<int> row_ptr((size_t)rows + 1), col_ind((size_t)std::max(nnz, 1));
-        std::vector<double> val((size_t)std::max(nnz, 1));
-        if (int rc = smvp_csr_from_coo(coo, rows, nnz, row_ptr.data(), col_ind.data(), val.data()))
-            return rc;
-        if (int rc = smvp_csr_create(&s.csr, o->device, rows, cols, nnz, row_ptr.data(), col_ind.data(), val.data(),
-                                     SMVP_MEM_HOST, nullptr))
-            return rc;
-    }
-    if (o->csr_kernel != SMVP_CSR_KERNEL_AUTO || o->csr_param != 0)
-        if (int rc = smvp_csr_set_kernel(s.csr, o->csr_kernel, o->csr_param))
-            return rc;
-    if (int rc = prepare_run(s, rows, cols, iters, o))
-        return rc;
-
-    // The reference clears y before every product, outside its timed window (main-cli.c:405).  Every CSR kernel
-    // here overwrites all of y, so nothing is cleared per product; y is poisoned with NaN once instead, so that a
-    // kernel that skipped a row could not hide behind a cleared (or an earlier) result.
-    HIP_TRY(hipMemsetAsync(s.d_y, 0xff, sizeof(double) * (size_t)std::max(rows, 1), s.stream));
-    smvp_csr_t *A = s.csr;
-    const int slots = csr_can_stamp(A) ? smvp::owner_stamp_slots(A->ntiles, A->flavor) : 0;
-    const int rgrid = slots > 0 ? csr_repeat_grid(A) : 0;  // the tile kernel's repeating form: n products per launch
-    if (int rc = run_timed_products(
-            s, rows, iters, o, slots, [](double *) { return (int)SMVP_OK; },
-            [A, &s](const double *x, double *yy, unsigned long long *stamps) { return csr_spmv_impl(A, x, yy, s.stream, stamps); }, rgrid,
-            [A, &s](const double *x, double *yy, unsigned long long *stamps, int reps, int grid, unsigned *ctl, bool first, unsigned long long patience) {
-                return csr_spmv_repeat(A, x, yy, s.stream, stamps, reps, grid, ctl, first, patience);
-            }))
-        return rc;
-    return finish_run(s, rows, iters, y, time_each_ms, stats);
-}
-
-extern "C" int smvp_tjds_compute(const smvp_coo_t *coo, int rows, int cols, int nnz, int iters,
-                                 const smvp_run_opts_t *opts, double *y, double *time_each_ms,
-                                 smvp_time_stats_t *stats)
-{
-    smvp_run_opts_t def;
-    smvp_run_opts_default(&def);
-    const smvp_run_opts_t *o = opts ? opts : &def;
-    if (iters < 1 || rows < 0 || cols < 0 || nnz < 0 || (rows > 0 && !y))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_compute: bad argument");
-    if (int rc = check_iterate(o, rows, cols))
-        return rc;
-    if (o->iterate && o->tjds_ref_quirks)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "ref-quirks TJDS indexes the operand by row: it has no meaning for a changing operand");
-    if (o->ngpus > 1) {
-        if (o->tjds_ref_quirks)
-            return smvp::fail(SMVP_ERR_UNSUPPORTED, "ref-quirks TJDS is a whole-matrix artefact: use one GPU");
-        return sharded_compute(true, coo, rows, cols, nnz, iters, o, y, time_each_ms, stats);
-    }
-    if (int rc = usable_device(o->device))
-        return rc;
-    DeviceScope on(o->device);
-
-    int num_diag = 0, ref_num = 0, last_single = 0;
-    RunScratch s;
-    if (o->convert_on_device) {
-        const int cap = std::max(rows, nnz) + 2;
-        HIP_TRY(hipMalloc(&s.d_coo, sizeof(smvp_coo_t) * (size_t)std::max(nnz, 1)));
-        HIP_TRY(hipMalloc((void **)&s.d_i0, sizeof(int) * (size_t)std::max(cols, 1)));   // perm
-        HIP_TRY(hipMalloc((void **)&s.d_i1, sizeof(int) * (size_t)std::max(nnz, 1)));    // row_ind
-        HIP_TRY(hipMalloc((void **)&s.d_i2, sizeof(int) * (size_t)cap));                 // start_pos
-        HIP_TRY(hipMalloc((void **)&s.d_v, sizeof(double) * (size_t)std::max(nnz, 1)));
-        if (nnz > 0)
-            HIP_TRY(hipMemcpy(s.d_coo, coo, sizeof(smvp_coo_t) * (size_t)nnz, hipMemcpyHostToDevice));
-        if (int rc = smvp_tjds_from_coo_device((const smvp_coo_t *)s.d_coo, rows, cols, nnz, s.d_i0, s.d_i2, cap, s.d_i1,
-                                               s.d_v, &num_diag, &ref_num, &last_single, nullptr))
-            return rc;
-        if (int rc = smvp_tjds_create(&s.tjds, o->device, rows, cols, nnz, num_diag, s.d_i0, s.d_i2, s.d_i1, s.d_v,
-                                      SMVP_MEM_DEVICE))
-            return rc;
-    } else {
-        std::vector<int> perm((size_t)std::max(cols, 1)), start_pos((size_t)std::max(rows, nnz) + 2),
-            row_ind((size_t)std::max(nnz, 1));
-        std::vector<double> val((size_t)std::max(nnz, 1));
-        if (int rc = smvp_tjds_from_coo(coo, rows, cols, nnz, perm.data(), start_pos.data(), (int)start_pos.size(),
-                                        row_ind.data(), val.data(), &num_diag, &ref_num, &last_single))
-            return rc;
-        if (int rc = smvp_tjds_create(&s.tjds, o->device, rows, cols, nnz, num_diag, perm.data(), start_pos.data(),
-                                      row_ind.data(), val.data(), SMVP_MEM_HOST))
-            return rc;
-    }
-    if (o->tjds_ref_quirks)
-        if (int rc = smvp_tjds_set_ref_quirks(s.tjds, 1, ref_num, last_single))
-            return rc;
-    if (int rc = prepare_run(s, rows, cols, iters, o))
-        return rc;
-    if (int rc = smvp_tjds_set_x(s.tjds, s.d_x, s.stream))  // main-cli.c:907-923, setup
-        return rc;
-
-    if (o->tjds_mode != SMVP_TJDS_MODE_AUTO)
-        if (int rc = smvp_tjds_set_mode(s.tjds, o->tjds_mode))
-            return rc;
-    HIP_TRY(hipMemsetAsync(s.d_y, 0xff, sizeof(double) * (size_t)std::max(rows, 1), s.stream));  // NaN, as in the CSR path
-    smvp_tjds_t *T = s.tjds;
-    const int slots = tjds_can_stamp(T) ? smvp::owner_stamp_slots(T->rg->ntiles, T->rg->flavor) : 0;
-    bool first = true;
-    const bool iterate = o->iterate != 0;
-    if (int rc = run_timed_products(
-            s, rows, iters, o, slots,
-            [T, &s](double *yy) { return smvp_tjds_zero_y(T, yy, s.stream); },  // main-cli.c:1008, outside the window
-            [T, &s, &first, iterate](const double *x, double *yy, unsigned long long *stamps) {
-                if (iterate && !first)  // a new operand: its permutation is part of this product
-                    if (int rc = smvp_tjds_set_x(T, x, s.stream))
-                        return rc;
-                first = false;
-                return tjds_spmv_impl(T, yy, s.stream, stamps);
-            },
-            slots > 0 ? csr_repeat_grid(T->rg) : 0,  // (tjds_can_stamp: the row-gather product, which overwrites y and needs no `pre`)
-            [T, &s](const double *, double *yy, unsigned long long *stamps, int reps, int grid, unsigned *ctl, bool first, unsigned long long patience) {
-                return csr_spmv_repeat(T->rg, T->d_x_perm, yy, s.stream, stamps, reps, grid, ctl, first, patience);
-            }))
-        return rc;
-    return finish_run(s, rows, iters, y, time_each_ms, stats);
-}
