@@ -48,16 +48,16 @@ def serial_rows(name, row_ptr, ascending):
     return np.zeros(len(lens), dtype=bool)
 
 
-def csr_paths(rows, cols, row_ptr, col_ind, val, only_serial=False):
+def csr_paths(rows, cols, row_ptr, col_ind, val, only_serial=False, first_row=0):
     """(label, run, serial-rows mask or None for "not reproducible", kernel name) of every CSR path, one after the other; run(dx,
-    dy) enqueues one product."""
+    dy) enqueues one product.  first_row: the handles are row blocks (smvp_csr_create_block)."""
     ascending = bool(np.all((np.diff(col_ind.astype(np.int64)) > 0) | (np.diff(sv.row_of_entries(row_ptr)) > 0))) if len(col_ind) > 1 else True
 
     def path(A, label):
         name = A.describe()[0]
         return label, (lambda dx, dy: A.spmv(dx, dy)), serial_rows(name, row_ptr, ascending), name
 
-    A = sm.CsrMatrix(rows, cols, row_ptr, col_ind, val)
+    A = sm.CsrMatrix(rows, cols, row_ptr, col_ind, val, first_row=first_row)
     try:
         settings = [("AUTO", sm.CSR_KERNEL_AUTO, 0)] + [("kernel %d param %d" % kp, kp[0], kp[1]) for kp in CSR_VARIANTS] + \
                    [("COLSWEEP 1024 rows, %d parts" % p, sm.CSR_KERNEL_COLSWEEP, sm.sweep_parts(1024, p)) for p in (2, 4, 8)]
@@ -72,7 +72,7 @@ def csr_paths(rows, cols, row_ptr, col_ind, val, only_serial=False):
     for col16 in (1, 0):
         for rowrel in (None, 0):
             with sm.option("csr_col16", col16), sm.option("csr_rowrel", rowrel):
-                A = sm.CsrMatrix(rows, cols, row_ptr, col_ind, val)
+                A = sm.CsrMatrix(rows, cols, row_ptr, col_ind, val, first_row=first_row)
                 try:
                     A.set_kernel(sm.CSR_KERNEL_STREAM, 1024)
                     yield path(A, "STREAM 1024, csr_col16 %r, csr_rowrel %r" % (col16, rowrel))
@@ -82,7 +82,7 @@ def csr_paths(rows, cols, row_ptr, col_ind, val, only_serial=False):
         return
     for near in (0, 1):
         with sm.option("binned_near", near):
-            A = sm.CsrMatrix(rows, cols, row_ptr, col_ind, val)
+            A = sm.CsrMatrix(rows, cols, row_ptr, col_ind, val, first_row=first_row)
             try:
                 A.set_kernel(sm.CSR_KERNEL_BINNED, 0)
                 yield path(A, "BINNED band 0, binned_near %d" % near)
