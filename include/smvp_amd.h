@@ -451,6 +451,40 @@ int smvp_tjds_spmm_transposed(smvp_tjds_t *h, int k, const double *d_X, long lon
  * of passes.  (The leading dimensions are not known here: for k = 1 the symbol is the one-lane pass's; a call with k = 1 and
  * ldx = ldy = 1 runs smvp_tjds_spmv_transposed's kernel, which gives the same bits.) */
 int smvp_tjds_spmm_transposed_describe(const smvp_tjds_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes);
+/* The forward block product from a TJDS handle, kernel K10: d_Y[r*ldy + v] = (A X)(r, v) for r < rows, v < k.  For an M x N
+ * matrix X is N x k and Y is M x k, both row-major doubles with leading dimensions ldx >= k, ldy >= k: the operand conventions of
+ * smvp_csr_spmm (a contiguous (n, k) array, or a slice of columns of a wider one; column-major operands are not supported).
+ *   - Bits: Y(r, v) = acc, where acc = 0.0 and then, for the stored positions j with row_ind[j] == r in ascending TJDS position
+ *     j: acc += val[j] * X(perm[j - start_pos[d(j)]], v), d(j) being the jagged diagonal that holds j and each product rounded
+ *     before the add (-ffp-contract=off) -- the corrected product of main-cli.c:1013-1020 run serially on column v of X.  It
+ *     holds for every row length, k, ldx and ldy, on every stream, the same bits on every run.  It is the order of summation
+ *     smvp_tjds_spmv documents for ROW_GATHER and TWO_PHASE, kept serially on rows of every length; bit equality with
+ *     smvp_tjds_spmv itself is not promised (its tile kernel keeps the serial order only on short rows).
+ *   - Writes: Y(r, v) for v < k is overwritten (no pre-zeroing); a row without entries gets +0.0; Y(r, v) for k <= v < ldy is
+ *     never touched; Y never holds -0.0.
+ *   - Values: as stated at smvp_csr_spmv -- an element of X influences exactly the rows that store an entry in its column (a slot
+ *     past a row's end is left out with a select and never multiplied by 0); stored zeros are multiplied; subnormals are kept.
+ *   - State: the call reads nothing of smvp_tjds_set_x's operand, any mode's plan, the value cache or the ref-quirks edit, so its
+ *     result does not depend on smvp_tjds_set_mode / set_tile / set_value_cache / set_ref_quirks; a forward smvp_tjds_spmv after
+ *     it gives the bits it gave before it, without a new smvp_tjds_set_x.
+ *   - Plan: the first call on a handle builds the SpMM plan on the device and synchronises `stream`; later calls are
+ *     asynchronous on `stream`.  The plan is the entries regrouped by row: ptr[rows + 1]; pos[nnz], the TJDS positions, ascending
+ *     inside a row; col[nnz], the original column perm[pos - start_pos[d]]; and smvp_csr_spmm's one int per row (rows longest
+ *     first inside blocks of 4096 rows, stable) -- 4 (rows + 1) + 8 nnz + 4 rows bytes in buffers of its own, shared with no
+ *     mode's plan and freed by smvp_tjds_destroy.  smvp_tjds_plan_info does not count it: its bytes and build time come out of
+ *     smvp_tjds_spmm_describe.  val is read through pos, not copied: with adopted arrays (SMVP_MEM_DEVICE) val changed in place is
+ *     seen by the next call without any other call; row_ind, start_pos and perm may not be changed.
+ *   - The matrix is read once per 16 vectors: ceil(k / 16) passes.
+ *   - SMVP_ERR_INVALID, before anything is enqueued, for: a NULL handle; k < 1, ldx < k or ldy < k; a NULL d_X with nnz > 0 or
+ *     a NULL d_Y with rows > 0; byte ranges of X ((cols - 1) ldx + k doubles) and Y ((rows - 1) ldy + k doubles) that overlap; a
+ *     capturing stream on a handle whose SpMM plan is not built yet (the capture stays valid and nothing is written: make one
+ *     call outside the capture first). */
+int smvp_tjds_spmm(smvp_tjds_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream);
+/* The kernel symbols of a product with k vectors (one per pass, joined by " + ", cut at `cap`), its algorithmic bytes
+ * 12 nnz + 4 (D + 1) + 4 cols + 8 k (rows + cols) whatever the number of passes, and in `plan` (may be NULL) the SpMM plan's bytes
+ * 4 (rows + 1) + 8 nnz + 4 rows and build time -- zero until the first smvp_tjds_spmm, as for smvp_csr_spmm_describe.
+ * SMVP_ERR_INVALID for a NULL handle or k < 1, with the outputs untouched. */
+int smvp_tjds_spmm_describe(const smvp_tjds_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes, smvp_plan_info_t *plan);
 void smvp_tjds_destroy(smvp_tjds_t *h);
 
 /* ------------------------------------------- several GPUs, one host process */

@@ -1290,6 +1290,15 @@ struct smvp_tjds {
     int *d_inv_pos = nullptr;    // nnz: positions j grouped by row_ind[j], ascending inside a row
     smvp_csr *inv = nullptr;     // unit-value CSR over (inv_ptr, inv_pos), x = prod
 
+    // smvp_tjds_spmm (K10, smvp_tjds_spmm.hip): the entries regrouped by row in buffers of its own (not the two plans' above: they
+    // come and go with the modes), built by the first call and kept whatever the mode is
+    int *d_mm_ptr = nullptr;     // rows + 1
+    int *d_mm_pos = nullptr;     // nnz: TJDS positions, ascending inside a row
+    int *d_mm_col = nullptr;     // nnz: the original column perm[pos - start_pos[d]]
+    int *d_mm_order = nullptr;   // rows: K7's row order
+    bool mm_planned = false;
+    double mm_build_ms = 0.0;
+
     // launch plan (rebuilt when ref-quirks mode changes)
     bool quirks = false;
     int *d_plan_start_pos = nullptr;  // start_pos as the kernel should see it
@@ -1678,6 +1687,64 @@ extern "C" int smvp_tjds_spmm_transposed_describe(const smvp_tjds_t *h, int k, c
     return SMVP_OK;
 }
 
+// K10: Y = A X for k vectors from the handle's own arrays (the true start_pos, not the ref-quirks edit) through a plan of its own
+// and the caller's X: no x_perm, no mode's plan, no value cache is read or written.  Every argument is checked before anything
+// is enqueued; the first call builds the plan (and synchronises `stream`).
+extern "C" int smvp_tjds_spmm(smvp_tjds_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: null handle");
+    if (k < 1 || ldx < k || ldy < k)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: k = %d, ldx = %lld, ldy = %lld (need k >= 1, ldx >= k, ldy >= k)", k, ldx, ldy);
+    if ((h->nnz > 0 && !d_X) || (h->rows > 0 && !d_Y))
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: null %s", h->rows > 0 && !d_Y ? "d_Y" : "d_X");
+    if (operands_overlap(d_X, ldx, h->cols, d_Y, ldy, h->rows, k))  // X(c, v) for c < cols, Y(r, v) for r < rows (v < k)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: the byte ranges of d_X and d_Y overlap");
+    DeviceScope on(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->mm_planned) {
+        if (int rc = refuse_capture(st, "smvp_tjds_spmm: the first call on a handle builds its plan and cannot be captured "
+                                        "(call it once outside the capture)"))
+            return rc;
+        const double t0 = wall_ms();
+        const size_t n = (size_t)std::max(h->nnz, 4);  // (buffers kept from a call whose build failed are used again)
+        if ((!h->d_mm_ptr && hipMalloc((void **)&h->d_mm_ptr, ((size_t)h->rows + 4) * sizeof(int)) != hipSuccess) ||
+            (!h->d_mm_pos && hipMalloc((void **)&h->d_mm_pos, n * sizeof(int)) != hipSuccess) ||
+            (!h->d_mm_col && hipMalloc((void **)&h->d_mm_col, n * sizeof(int)) != hipSuccess) ||
+            (!h->d_mm_order && hipMalloc((void **)&h->d_mm_order, (size_t)std::max(h->rows, 4) * sizeof(int)) != hipSuccess))
+            return smvp::fail(SMVP_ERR_ALLOC, "smvp_tjds_spmm: cannot allocate the plan (%d rows, %d entries)", h->rows, h->nnz);
+        if (int rc = smvp::build_tjds_spmm_plan(h->d_row_ind, h->d_start_pos, h->d_perm, h->num_diag, h->nnz, h->rows, h->d_mm_ptr,
+                                                h->d_mm_pos, h->d_mm_col, h->d_mm_order, st))
+            return rc;
+        h->mm_planned = true;
+        h->mm_build_ms = wall_ms() - t0;
+    }
+    const hipError_t e = smvp::launch_tjds_spmm(h->d_mm_ptr, h->d_mm_pos, h->d_mm_col, h->d_val, h->d_mm_order, d_X, ldx, d_Y, ldy,
+                                                h->rows, k, st);
+    if (e != hipSuccess)
+        return smvp::fail(SMVP_ERR_HIP, "smvp_tjds_spmm: launch failed: %s", hipGetErrorString(e));
+    return SMVP_OK;
+}
+
+extern "C" int smvp_tjds_spmm_describe(const smvp_tjds_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes, smvp_plan_info_t *plan)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_describe: null handle");
+    if (k < 1)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_describe: k = %d (need k >= 1)", k);
+    if (kernel_name && cap)
+        smvp::tjds_spmm_kernel_name(k, kernel_name, cap);
+    const double matrix = 12.0 * h->nnz + 4.0 * (h->num_diag + 1.0) + 4.0 * h->cols;
+    if (alg_bytes)
+        *alg_bytes = matrix + 8.0 * k * ((double)h->rows + h->cols);
+    if (plan) {
+        plan->matrix_bytes = matrix;
+        plan->plan_bytes = h->mm_planned ? 4.0 * (h->rows + 1.0) + 8.0 * h->nnz + 4.0 * h->rows : 0.0;
+        plan->build_ms = h->mm_planned ? h->mm_build_ms : 0.0;
+    }
+    return SMVP_OK;
+}
+
 // Which values the one-kernel product keeps a second copy of: those of val lines whose 16 entries belong to
 // `min_tiles` tiles or more (0: none -- every value is read from val itself).  Rebuilds the plan.
 extern "C" int smvp_tjds_set_value_cache(smvp_tjds_t *h, int min_tiles)
@@ -1750,7 +1817,8 @@ extern "C" void smvp_tjds_destroy(smvp_tjds_t *h)
     if (h->d_work)
         (void)hipFree(h->d_work);
     smvp_csr_destroy(h->inv);
-    for (void *p : {(void *)h->d_prod, (void *)h->d_inv_ptr, (void *)h->d_inv_pos})
+    for (void *p : {(void *)h->d_prod, (void *)h->d_inv_ptr, (void *)h->d_inv_pos, (void *)h->d_mm_ptr, (void *)h->d_mm_pos,
+                    (void *)h->d_mm_col, (void *)h->d_mm_order})
         if (p)
             (void)hipFree(p);
     delete h;

@@ -47,6 +47,14 @@ const char *tjds_transposed_kernel_name();
 hipError_t launch_tjds_spmm_transposed(const int *start_pos, const int *row_ind, const double *val, const int *perm, const double *X,
                                        long long ldx, double *Y, long long ldy, int cols, int num_diag, int k, hipStream_t stream);
 void tjds_spmm_transposed_kernel_name(int k, char *name, size_t cap);  // the passes' kernel symbols
+// K10 (smvp_tjds_spmm.hip): Y = A X for k vectors from a TJDS handle -- K7's walk over the entries regrouped by row, the value
+// read through the entry's TJDS position; kSpmmMaxVectors vectors per pass.  The plan: ptr[rows + 1], pos[nnz] (TJDS positions,
+// ascending inside a row), col[nnz] (original columns), order[rows] (build_spmm_order on ptr), all built on the device
+int build_tjds_spmm_plan(const int *row_ind, const int *start_pos, const int *perm, int num_diag, int nnz, int rows, int *ptr,
+                         int *pos, int *col, int *order, hipStream_t stream);  // SMVP status; synchronises `stream`
+hipError_t launch_tjds_spmm(const int *ptr, const int *pos, const int *col, const double *val, const int *order, const double *X,
+                            long long ldx, double *Y, long long ldy, int rows, int k, hipStream_t stream);
+void tjds_spmm_kernel_name(int k, char *name, size_t cap);  // the passes' kernel symbols
 // smvp_csr_create_transposed (smvp_convert_device.hip): the entries of a CSR matrix with row and column swapped, storage order
 hipError_t launch_csr_swapped_coo(const int *row_ptr, const int *col_ind, const double *val, int rows, int nnz, smvp_coo_t *coo,
                                   hipStream_t stream);

@@ -119,7 +119,7 @@ EXPORTS = [
     "smvp_csr_create", "smvp_csr_create_block", "smvp_csr_far_share", "smvp_csr_set_kernel", "smvp_csr_get_kernel", "smvp_csr_gather_spread", "smvp_csr_spmv",
     "smvp_csr_describe", "smvp_csr_plan_launches", "smvp_csr_destroy", "smvp_csr_spmm", "smvp_csr_spmm_describe",
     "smvp_csr_create_transposed", "smvp_csr_device_arrays", "smvp_tjds_spmv_transposed", "smvp_tjds_transposed_describe",
-    "smvp_tjds_spmm_transposed", "smvp_tjds_spmm_transposed_describe",
+    "smvp_tjds_spmm_transposed", "smvp_tjds_spmm_transposed_describe", "smvp_tjds_spmm", "smvp_tjds_spmm_describe",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -165,6 +165,8 @@ def lib():
         L.smvp_tjds_transposed_describe.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_double)]
         L.smvp_tjds_spmm_transposed.argtypes = [vp, ci, vp, C.c_longlong, vp, C.c_longlong, vp]
         L.smvp_tjds_spmm_transposed_describe.argtypes = [vp, ci, C.c_char_p, C.c_size_t, C.POINTER(C.c_double)]
+        L.smvp_tjds_spmm.argtypes = [vp, ci, vp, C.c_longlong, vp, C.c_longlong, vp]
+        L.smvp_tjds_spmm_describe.argtypes = [vp, ci, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(PlanInfo)]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -666,6 +668,23 @@ class TjdsMatrix:
         b = C.c_double()
         _check(lib().smvp_tjds_spmm_transposed_describe(self._h, k, name, 256, C.byref(b)), "smvp_tjds_spmm_transposed_describe")
         return name.value.decode(), b.value
+
+    def spmm(self, X, Y, stream=None):
+        """Y = A X for k vectors at once from a TJDS handle (smvp_tjds_spmm, K10): X (cols x k) and Y (rows x k) are float64
+        CUDA tensors with stride(1) == 1, ldx = X.stride(0), ldy = Y.stride(0).  Every column of Y is the serial sum over the
+        row in TJDS position order.  Asynchronous on `stream`; needs no set_x; the first call builds the plan."""
+        k, ldx, ldy = spmm_operands(X, Y, self.rows, self.cols)
+        if not (X.is_cuda and Y.is_cuda):
+            raise ValueError("X and Y must be device tensors")
+        _check(lib().smvp_tjds_spmm(self._h, k, _dev_ptr(X), ldx, _dev_ptr(Y), ldy, _stream_ptr(stream)), "smvp_tjds_spmm")
+
+    def spmm_describe(self, k):
+        """(kernel symbols, algorithmic bytes for k vectors, {plan_bytes, build_ms} of the SpMM plan: 0 before the first spmm)."""
+        name = C.create_string_buffer(256)
+        b = C.c_double()
+        i = PlanInfo()
+        _check(lib().smvp_tjds_spmm_describe(self._h, k, name, 256, C.byref(b), C.byref(i)), "smvp_tjds_spmm_describe")
+        return name.value.decode(), b.value, {"plan_bytes": i.plan_bytes, "build_ms": i.build_ms}
 
     def set_mode(self, mode):
         _check(lib().smvp_tjds_set_mode(self._h, mode), "smvp_tjds_set_mode")
