@@ -547,7 +547,13 @@ enum { SMVP_GATHER_NONE = 0, SMVP_GATHER_OVERLAPPED = 1, SMVP_GATHER_AFTER = 2 }
 int smvp_sharded_spmv(smvp_sharded_t *h, int allgather, int timed);
 int smvp_sharded_synchronize(smvp_sharded_t *h, double *ms_of_last_timed_product); /* max over the GPUs */
 /* power iteration: the gathered y (optionally divided by its largest magnitude) becomes x on every GPU;
- * call between two smvp_sharded_spmv(h, 1, ..), after which the all-gather is what feeds the next product */
+ * call between two smvp_sharded_spmv(h, 1, ..), after which the all-gather is what feeds the next product.
+ * Asynchronous, ordered behind the product on every GPU's stream: no smvp_sharded_synchronize is needed before or after it.
+ * normalize: the rule of smvp_run_opts_t.normalize, applied by every GPU to its own gathered copy (the same data, the same
+ * arithmetic: the same bits everywhere).  It is the gathered vectors (smvp_sharded_get_y(.., gathered = 1, ..)) that are
+ * normalised; the local slices (gathered = 0) keep the raw product.  Steps chained this way give, bit for bit, what the same
+ * handle gives when the caller reads the gathered y, normalises it and hands it back through smvp_sharded_set_x.
+ * SMVP_ERR_INVALID on a matrix that is not square; nothing is changed then. */
 int smvp_sharded_feed_back(smvp_sharded_t *h, int normalize);
 int smvp_sharded_get_y(smvp_sharded_t *h, int slot, int gathered, double *y_host);
 int smvp_sharded_info(const smvp_sharded_t *h, int *ngpus, int *rows_per_gpu); /* rows_per_gpu = the tallest block */
@@ -573,7 +579,14 @@ typedef struct smvp_run_opts {
     int ngpus;          /* 0 or 1: one GPU (`device`); N > 1: row blocks on GPUs 0..N-1 + RCCL all-gather of y */
     int iterate;        /* 1: power iteration, x_{k+1} = A x_k for `iters` steps -- the product the assignment asked
                            for (comment at main-cli.c:401); square matrices; y = the last iterate; each step timed */
-    int normalize;      /* with iterate: divide every iterate by its largest magnitude (keeps 1000 steps finite) */
+    int normalize;      /* with iterate: divide every iterate by its largest magnitude (keeps 1000 steps finite).  The divisor
+                           is the largest |element| among the elements that are not NaN; an iterate whose largest magnitude
+                           is 0 is left as it is (no 0 / 0); an infinite one turns the finite elements into zeros of their
+                           sign and the infinite ones into NaN; NaN elements stay NaN.  Each quotient is the correctly rounded
+                           IEEE quotient (subnormal divisors included), so the iterate is a pure function of the product.
+                           The iterated result is, bit for bit, that of the same handle's single products chained by the
+                           caller with this rule in between -- on every path whose product is reproducible from run to run
+                           (every CSR family, TJDS ROW_GATHER and TWO_PHASE, ngpus > 1; not TJDS ATOMIC) */
     int tjds_mode;      /* SMVP_TJDS_MODE_* for smvp_tjds_compute (AUTO = ROW_GATHER) */
     int timing;         /* SMVP_TIMING_*: how each product is timed */
     int shard_exchange; /* ngpus > 1: SMVP_EXCHANGE_* (default AUTO; COPIES / DIRECT: ngpus may exceed the visible GPUs -- virtual ranks) */

@@ -999,6 +999,8 @@ extern "C" int smvp_sharded_synchronize(smvp_sharded_t *h, double *ms)
             float t = 0.f;
             if (hipEventElapsedTime(&t, h->ev0[g], h->ev1[g]) == hipSuccess)
                 worst = std::max(worst, (double)t);
+            else  // no timed product yet: nothing to report -- and no error left behind for the next launch check to find
+                (void)hipGetLastError();
         }
     }
     if (ms)
