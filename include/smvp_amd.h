@@ -64,6 +64,9 @@ const char *smvp_version_string(void); /* "0.6.4" */
  * environment variable any more:
  *   "csr_col16" 0: the CSR tile kernel keeps 32-bit columns           "csr_rowrel" 0: its second phase reads row_ptr
  *   "binned_near" 1: the binned plan's near part on the tile kernel   "binned_overlap" 0: pass A behind the near part, one stream
+ *   "csr_sweep_alternate" 0: every product of the tile kernel sweeps its tiles forward; 1: a handle's plain launches alternate
+ *                            forward / backward whatever the size (default: where one product's bytes exceed the Infinity Cache);
+ *                            the results are the same bits either way
  *   "tjds_index" 0 | 1 | 2: 16-bit position words (default) / 32-bit sorted / 32-bit columns
  *   "sharded_threads" 1: the sharded layer's issuing threads with one GPU too     "mm_threads" n: the reader's threads (1 = serial)
  * Unknown names are SMVP_ERR_INVALID. */

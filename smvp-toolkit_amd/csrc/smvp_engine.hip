@@ -148,6 +148,11 @@ struct TilePlan {
     unsigned *d_word32 = nullptr;
     int *d_run_ptr = nullptr, *d_run_tab = nullptr;
     int runs_total = 0;
+    // STREAM: the direction of the next plain launch's sweep over the tiles.  It flips with every such launch (a handle is
+    // used by one stream at a time), so a product starts where the one before it ended -- on what the Infinity Cache still
+    // holds; sweep_alternate = 0 (a matrix the caches hold, or plan option "csr_sweep_alternate" 0; decided when the plan is
+    // built): always forward
+    int sweep_alternate = 1, sweep_backward = 0;
 };
 
 // COLSWEEP: the entries a second time, every strip sorted by column (built on the device); build_sweep_plan
@@ -536,6 +541,13 @@ void try_column_offsets(smvp_csr *h)
             (void)hipFree(p);
 }
 
+// A handle's plain launches of the tile kernel sweep the tiles forward and backward in turn where one product's algorithmic
+// bytes exceed this: a product then starts on what the one before it left in the 256 MiB Infinity Cache (a cyclic sweep over
+// more than the cache holds hits nothing).  Not below it: backward, XCD i takes the tiles XCD 7 - i had, so a matrix that
+// lives in the L2s or in the Infinity Cache finds its lines in another XCD's L2 -- memplus x16 (30 MB) ran 27 % slower
+// alternating, x40 / x100 (75 / 187 MB) 0.8 / 0.3 % slower, x200 (374 MB) 8 % faster (profiles/sweep_direction_measured.txt).
+constexpr double kSweepAlternateMinBytes = 256.0 * 1024 * 1024;
+
 int build_tile_plan(smvp_csr *h)
 {
     TilePlan &t = h->tile;
@@ -581,6 +593,10 @@ int build_tile_plan(smvp_csr *h)
         HIP_TRY(hipMemset(t.d_carry, 0, std::max(ntiles, 1) * sizeof(double)));
     }
     t.ntiles = ntiles;
+    // plan option: 0 = every product sweeps forward, 1 = the plain launches alternate whatever the size; default: they alternate
+    // where one product's bytes do not fit the Infinity Cache anyway (see kSweepAlternateMinBytes)
+    const int alternate = smvp::option("csr_sweep_alternate", -1);
+    t.sweep_alternate = alternate < 0 ? 12.0 * (double)h->nnz + 12.0 * h->rows + 8.0 * h->cols > kSweepAlternateMinBytes : alternate != 0;
     if (tile_ordered(h->flavor)) {
         // every tile's entries in TJDS order + what each tile reads past its end, in row order
         std::vector<int> ovf_ptr((size_t)ntiles + 1, 0);
@@ -998,6 +1014,10 @@ int smvp::csr_spmv_stamped(smvp_csr_t *h, const double *d_x, double *d_y, void *
     else if (h->kernel == SMVP_CSR_KERNEL_STREAM) {
         smvp::OwnerLaunch l{};
         fill_owner_launch(h, d_x, d_y, stamps, &l);
+        // the plain single launch, stamped or not, of a CSR handle, of a binned plan's near handle and of a TJDS handle's
+        // tile-ordered stream (all come through here): this one sweeps the way the last one did not
+        l.backward = h->tile.sweep_backward;
+        h->tile.sweep_backward = h->tile.sweep_alternate ? !l.backward : 0;
         e = smvp::launch_csr_stream_owner(h->vpt, owner_flavor(h), l, st);
     } else
         e = smvp::launch_csr_stream(h->vpt, h->d_row_ptr, h->d_col_ind, h->d_val, d_x, d_y, h->tile.d_tile_row,

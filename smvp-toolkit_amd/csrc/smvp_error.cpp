@@ -36,6 +36,8 @@ struct Option { const char *name; std::atomic<int> value; };
 Option g_options[] = {
     {"csr_col16", {-1}},        // 0: the CSR tile kernel keeps col_ind's 32-bit columns (default: 16-bit offsets where a tile's columns lie close)
     {"csr_rowrel", {-1}},       // 0: the tile kernel's second phase reads row_ptr (default: its own 16-bit row offsets)
+    {"csr_sweep_alternate", {-1}},  // 0: every product of the tile kernel sweeps its tiles forward; 1: a handle's plain launches alternate forward / backward
+                                    // whatever the size (default: they alternate where one product's bytes exceed the Infinity Cache)
     {"binned_near", {-1}},      // 1: the binned plan's near part runs on the tile kernel (default 0: csr_near_window where it suits)
     {"binned_overlap", {-1}},   // 0: pass A behind the near part on one stream (default 1: beside it on a stream of its own)
     {"tjds_index", {-1}},       // the one-kernel TJDS product's index stream: 0 = 16-bit position words (default), 1 = 32-bit sorted, 2 = 32-bit columns

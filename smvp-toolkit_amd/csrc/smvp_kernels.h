@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "smvp_amd.h"
+#include "smvp_tile_map.h"  // tile_of_block, tile_of_block_swept: which tile a workgroup takes (host-testable)
 
 namespace smvp {
 
@@ -21,14 +22,6 @@ constexpr int kSweepRowBits = 13;  // a strip holds at most 8192 rows (64 KB of 
 constexpr int kSweepTurnCap = (1 << (16 - kSweepRowBits)) - 1;  // ... and the 16-bit row word carries the entry's turn, capped
 constexpr int kTjdsBlock = 256;     // permuted columns per work item
 constexpr int kTjdsDiagChunk = 8;   // jagged diagonals per work item
-
-// Blocks are dealt round-robin over the 8 XCDs; XCD i takes `group` consecutive tiles out of every run of 8 * group
-// (the measurements are beside K2 in smvp_kernels.hip)
-__device__ __forceinline__ int tile_of_block(int block, int group)
-{
-    const int xcd = block & 7, seq = block >> 3;
-    return (seq / group) * (8 * group) + xcd * group + seq % group;
-}
 
 // K7 (smvp_spmm.hip): k products that share one read of the matrix
 constexpr int kSpmmMaxVectors = 16;    // vectors per pass (16 doubles: one 128-byte line of X per gathered column)
@@ -94,6 +87,7 @@ struct OwnerLaunch {
     const int *run_ptr = nullptr, *run_tab = nullptr;
     const unsigned short *row_rel = nullptr;   // rows' first entries relative to their tile's (or nullptr: row_ptr is read)
     int rows = 0, nnz = 0, ntiles = 0;
+    int backward = 0;   // plain launches: sweep the tiles from the last to the first (tile_of_block_swept; the repeating launch ignores it)
 };
 hipError_t launch_csr_stream_owner(int vpt, int flavor, const OwnerLaunch &l, hipStream_t stream);
 // diagnostic builds (make HIPFLAGS+=-DSMVP_PHASE_STAMPS): print and clear the mean time a workgroup of the owner kernel / of

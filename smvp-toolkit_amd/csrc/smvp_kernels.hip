@@ -43,7 +43,12 @@ __device__ __forceinline__ double shfl_down_sum(double v)
 // (one XCD per contiguous eighth of the matrix was 60.1 %).  64 keeps the speed of
 // the small groups and most of the traffic saving of the large ones.
 // Speed only: any placement gives the same result.  (tile_of_block itself lives in
-// smvp_kernels.h: K7, smvp_spmm.hip, deals its row blocks the same way.)
+// smvp_tile_map.h: K7, smvp_spmm.hip, deals its row blocks the same way.)
+// The owner kernel deals its tiles in either direction, tile_of_block_swept: the plain launches of a
+// handle whose matrix is larger than the 256 MiB Infinity Cache alternate, so a product starts on the
+// tiles the one before it touched last -- what the cache still holds (DESIGN.md section 4, K2:
+// memplus x944 +4.2 %, x300 +10.3 %; a matrix the caches hold keeps the forward sweep, where every
+// XCD finds its own tiles in its L2).
 
 #ifndef SMVP_TU_ILP
 // ---------------------------------------------------------------------------
@@ -244,6 +249,8 @@ struct OwnerExtra {
     const unsigned short *row_rel = nullptr;  // every row's first entry relative to the first entry of the tile it
                                     // starts in (2 B per row read by the product instead of row_ptr's 4); nullptr: row_ptr itself
     unsigned long long *stamps = nullptr;     // STAMPED: per-wave {first, last} wall-clock ticks of this launch
+    int back_grid = 0;                  // 0: the tiles are swept forward; else the launch's grid, and they are swept backward
+                                    // (tile_of_block_swept; set by the plain launcher alone, the repeating launch stays forward)
 };
 
 // The ONE place an OwnerExtra is filled from a launch description (the plain launcher, the ILP unit's launcher through it, the
@@ -375,7 +382,7 @@ __device__ __forceinline__ void owner_body(
         return;                                                   \
     } while (0)
 
-    const int b = tile_of_block(block, tile_group_arg);
+    const int b = tile_of_block_swept(block, tile_group_arg, ex.back_grid);
     if (b >= ntiles)
         SMVP_OWNER_EXIT();
     const int nnz = nnz_arg;
@@ -1135,12 +1142,8 @@ hipError_t launch_csr_vector(int lanes_per_row, const int *row_ptr, const int *c
 // Tiles per XCD turn for a launch of `ntiles` tiles: kStreamTileGroup, smaller for small matrices so that
 // the grid (rounded up to a multiple of 8 * group) is not mostly empty blocks.
 // (Groups of 1 ... 2048 were swept in rounds 2 and 5 -- within 2 % from 16 on; profiles/HISTORY_r01_r04.md.)
-static int tile_group(int ntiles, int wanted = kStreamTileGroup)
-{
-    const int g = wanted;
-    const int fit = ntiles / 64;
-    return fit < 1 ? 1 : (fit < g ? fit : g);
-}
+// (The arithmetic lives in smvp_tile_map.h, where the host tests it.)
+static int tile_group(int ntiles, int wanted = kStreamTileGroup) { return tile_group_of(ntiles, wanted); }
 
 hipError_t launch_csr_stream(int vpt, const int *row_ptr, const int *col_ind, const double *val,
                              const double *x, double *y, const int *tile_row, const int *carry_row,
@@ -1174,7 +1177,7 @@ hipError_t launch_csr_stream(int vpt, const int *row_ptr, const int *col_ind, co
 }
 
 // grid of a launch of `ntiles` tiles (a multiple of 8 * group, see tile_of_block)
-static unsigned owner_grid(int ntiles, int group) { return (unsigned)((ntiles + 8 * group - 1) / (8 * group)) * 8u * group; }
+static unsigned owner_grid(int ntiles, int group) { return tile_grid_of(ntiles, group); }
 
 // tiles per XCD turn by flavour.  CSR measured best at 64 (profiles/r01_tile_group_sweep.txt).  The tile-ordered TJDS stream: the
 // group decides how often x_perm crosses the fabric -- a copy of memplus is 61 tiles, every XCD that gets some of them pulls
@@ -1194,7 +1197,8 @@ hipError_t launch_csr_stream_owner(int vpt, int flavor, const OwnerLaunch &l, hi
         return hipSuccess;
     const int group = tile_group(l.ntiles, flavor_group(flavor));
     const dim3 grid(owner_grid(l.ntiles, group));
-    const OwnerExtra ex = owner_extra_of(l, l.stamps);
+    OwnerExtra ex = owner_extra_of(l, l.stamps);
+    ex.back_grid = l.backward ? (int)grid.x : 0;  // (both units' kernels read it: the ILP unit launches with this `ex`)
 #define SMVP_OWNER_ST(V, F, S)                                                                                     \
     hipLaunchKernelGGL((csr_stream_owner<V, F, S>), grid, dim3(kStreamBlock), 0, stream, l.row_ptr, l.col_ind, l.val, \
                        l.x, l.y, l.tile_row, l.tile_next, l.rows, l.nnz, l.ntiles, group, ex)
