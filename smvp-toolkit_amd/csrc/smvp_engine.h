@@ -1,8 +1,17 @@
-// smvp_engine.h -- what the timed run (smvp_run.hip) needs of the handles (smvp_engine.hip), without their layout.
+// smvp_engine.h -- what the files around the CSR handle (smvp_engine.hip) share with it, without its layout: the helpers of
+// both handle files, what a TJDS handle (smvp_tjds.hip) needs of its nested CSR handles, and what the timed run (smvp_run.hip)
+// needs of either handle.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdint>
+#include <ctime>
+#include <string>
+#include <vector>
+
 #include "smvp_common.h"
+#include "smvp_kernels.h"
 
 #define HIP_TRY(expr)                                                                       \
     do {                                                                                    \
@@ -31,6 +40,119 @@ struct DeviceScope {
 
 int usable_device(int device);
 
+// ---------------------------------------------------------------------------------------------- both handle files
+inline double wall_ms()
+{
+    timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
+}
+
+// `count` elements of host memory as a device array of its own (never shorter than four elements)
+template <class T>
+int upload(T **dst, const T *src, size_t count)
+{
+    HIP_TRY(hipMalloc((void **)dst, std::max<size_t>(count, 4) * sizeof(T)));
+    if (count)
+        HIP_TRY(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return SMVP_OK;
+}
+
+template <class T>
+int upload(T **dst, const std::vector<T> &src) { return upload(dst, src.data(), src.size()); }
+
+// a caller's array: adopted where it is on the device already, else uploaded
+template <class T>
+int to_device(T **dst, const T *src, size_t count, int mem_kind, bool *owned)
+{
+    *owned = mem_kind != SMVP_MEM_DEVICE;
+    if (*owned)
+        return upload(dst, src, count);
+    *dst = const_cast<T *>(src);
+    return SMVP_OK;
+}
+
+// The call allocates or synchronises: refused with `why` while `st` is capturing.
+inline int refuse_capture(hipStream_t st, const char *why)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return smvp::fail(SMVP_ERR_INVALID, "%s", why);
+    return SMVP_OK;
+}
+
+// Do the byte ranges of two operands meet?  An operand is n rows of k doubles, ld doubles from one row to the next (a vector:
+// ld = 1, k = 1); without rows it has no bytes.
+inline bool operands_overlap(const double *a, long long lda, int na, const double *b, long long ldb, int nb, int k)
+{
+    const unsigned __int128 a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    const unsigned __int128 a1 = a0 + (na > 0 ? ((unsigned __int128)(na - 1) * (unsigned long long)lda + (unsigned)k) * 8u : 0);
+    const unsigned __int128 b1 = b0 + (nb > 0 ? ((unsigned __int128)(nb - 1) * (unsigned long long)ldb + (unsigned)k) * 8u : 0);
+    return a && b && na > 0 && nb > 0 && a0 < b1 && b0 < a1;
+}
+
+// Device-resident index arrays are range-checked on the device (host arrays are checked on the host).
+inline int check_device_indices(const int *d_a, long long n, int limit, const char *what)
+{
+    if (n <= 0)
+        return SMVP_OK;
+    int *d_bad = nullptr, h_bad = 0;
+    HIP_TRY(hipMalloc((void **)&d_bad, sizeof(int)));
+    hipError_t e = hipMemset(d_bad, 0, sizeof(int));
+    if (e == hipSuccess)
+        e = smvp::launch_find_out_of_range(d_a, n, limit, d_bad, nullptr);
+    if (e == hipSuccess)
+        e = hipMemcpy(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost);
+    (void)hipFree(d_bad);
+    if (e != hipSuccess)
+        return smvp::fail(SMVP_ERR_HIP, "range check of %s failed: %s", what, hipGetErrorString(e));
+    if (h_bad)
+        return smvp::fail(SMVP_ERR_INVALID, "%s[%d] lies outside [0, %d)", what, h_bad - 1, limit);
+    return SMVP_OK;
+}
+
+// What every product of operands X (x_rows rows) and Y (y_rows rows) of k columns checks before anything is enqueued, in this
+// order: k and the leading dimensions, an operand that is needed and null, byte ranges that meet.  `fn` opens the message; a
+// one-vector product (k = 1, ld = 1: the first check cannot fail) names its operands d_x / d_y.
+inline int check_block_operands(const char *fn, int k, const double *X, long long ldx, int x_rows, const double *Y, long long ldy, int y_rows,
+                                int nnz, bool block = true)
+{
+    const char *xn = block ? "d_X" : "d_x", *yn = block ? "d_Y" : "d_y";
+    if (k < 1 || ldx < k || ldy < k)
+        return smvp::fail(SMVP_ERR_INVALID, "%s: k = %d, ldx = %lld, ldy = %lld (need k >= 1, ldx >= k, ldy >= k)", fn, k, ldx, ldy);
+    if ((nnz > 0 && !X) || (y_rows > 0 && !Y))
+        return smvp::fail(SMVP_ERR_INVALID, "%s: null %s", fn, y_rows > 0 && !Y ? yn : xn);
+    if (operands_overlap(X, ldx, x_rows, Y, ldy, y_rows, k))
+        return smvp::fail(SMVP_ERR_INVALID, "%s: the byte ranges of %s and %s overlap", fn, xn, yn);
+    return SMVP_OK;
+}
+
+// ------------------------------------------------------------------------- a TJDS handle and its nested CSR handles
+// what a TJDS flavour borrows from its smvp_tjds owner (set before the tile plan is built)
+struct TjdsSource {
+    const int *pos = nullptr;
+    const int *start_pos = nullptr;
+    int num_diag = 0;
+    // the two-phase product's second phase: `val` holds the products of the first phase (written anew before every launch: no value
+    // cache, overflow entries by position), the operand is the unit vector (no x gather)
+    bool unit_operand = false;
+};
+
+// A handle of a TJDS flavour (smvp_kernels.h kFlavorTjds*) over device arrays it borrows: planned for the owner kernel, released
+// with smvp_csr_destroy, re-tiled with smvp_csr_set_kernel.
+int csr_create_tjds(smvp_csr_t **out, int device, int rows, int cols, int nnz, const int *d_row_ptr, const int *d_col_ind,
+                    const double *d_val, int flavor, const TjdsSource &src);
+// The value cache of a tile-ordered stream (TilePlan::d_val_cache): its threshold and the entries it holds -- false, and zeros, for
+// a handle that has no such stream; and the tile plan built anew for another threshold (plan_build_ms is left as it is).
+bool csr_value_cache(const smvp_csr_t *h, int *min_tiles, long long *cached_entries);
+int csr_replan_value_cache(smvp_csr_t *h, int min_tiles);
+// the owner kernel as the handle launches it, with its template arguments: entries per thread, flavour (0, 0 without a handle), false
+std::string csr_owner_kernel_name(const smvp_csr_t *h);
+// bytes of device memory the current launch plan keeps beside row_ptr / col_ind / val
+double csr_plan_bytes(const smvp_csr_t *h);
+
+// ---------------------------------------------------------------------------------------------------- the timed run
 // Per format: the {first, last} tick pairs one stamped product writes (0: the current plan cannot time itself on the device -- see
 // StampTimer), the grid of the repeating launch (0: no such form), `reps` products in one launch of it, and one product whose
 // launch stamps its window (stamps == nullptr: the plain product).  The TJDS forms multiply the operand of smvp_tjds_set_x.

@@ -1,21 +1,24 @@
-// smvp_engine.hip -- device-resident matrices and their launch plans.
+// smvp_engine.hip -- the CSR handle: a device-resident CSR matrix and its launch plans.
 //
-// This file owns what the reference keeps in CSRData / TJDSData (main-cli.c:61-75) once it is in HBM, and the per-matrix
-// launch plans.  The conversion halves live in smvp_convert.cpp (host); the timed iteration loop and the two
-// reference-shaped compute entry points live in smvp_run.hip, which sees the handles through smvp_engine.h only.
+// This file owns what the reference keeps in CSRData (main-cli.c:61-66) once it is in HBM, and the per-matrix launch plans;
+// the TJDS handle (TJDSData, :70-75) lives in smvp_tjds.hip and nests handles of this file.  The conversion halves live in
+// smvp_convert.cpp (host); the timed iteration loop and the two reference-shaped compute entry points live in smvp_run.hip.
+// Both see this handle through smvp_engine.h only.
 #include "smvp_engine.h"
-#include "smvp_kernels.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <ctime>
-#include <string>
-#include <vector>
 
+using smvp::check_block_operands;
+using smvp::check_device_indices;
 using smvp::DeviceScope;
 using smvp::kMaxEntries;
+using smvp::refuse_capture;
+using smvp::TjdsSource;
+using smvp::to_device;
+using smvp::upload;
 using smvp::usable_device;
+using smvp::wall_ms;
 
 int smvp::usable_device(int device)
 {
@@ -27,94 +30,9 @@ int smvp::usable_device(int device)
     return SMVP_OK;
 }
 
-namespace {
-
-double wall_ms()
-{
-    timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
-}
-
-// `count` elements of host memory as a device array of its own (never shorter than four elements)
-template <class T>
-int upload(T **dst, const T *src, size_t count)
-{
-    HIP_TRY(hipMalloc((void **)dst, std::max<size_t>(count, 4) * sizeof(T)));
-    if (count)
-        HIP_TRY(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
-    return SMVP_OK;
-}
-
-template <class T>
-int upload(T **dst, const std::vector<T> &src) { return upload(dst, src.data(), src.size()); }
-
-// a caller's array: adopted where it is on the device already, else uploaded
-template <class T>
-int to_device(T **dst, const T *src, size_t count, int mem_kind, bool *owned)
-{
-    *owned = mem_kind != SMVP_MEM_DEVICE;
-    if (*owned)
-        return upload(dst, src, count);
-    *dst = const_cast<T *>(src);
-    return SMVP_OK;
-}
-
-// The call allocates or synchronises: refused with `why` while `st` is capturing.
-int refuse_capture(hipStream_t st, const char *why)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(st, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-        return smvp::fail(SMVP_ERR_INVALID, "%s", why);
-    return SMVP_OK;
-}
-
-// Do the byte ranges of two operands meet?  An operand is n rows of k doubles, ld doubles from one row to the next (a vector:
-// ld = 1, k = 1); without rows it has no bytes.
-bool operands_overlap(const double *a, long long lda, int na, const double *b, long long ldb, int nb, int k)
-{
-    const unsigned __int128 a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    const unsigned __int128 a1 = a0 + (na > 0 ? ((unsigned __int128)(na - 1) * (unsigned long long)lda + (unsigned)k) * 8u : 0);
-    const unsigned __int128 b1 = b0 + (nb > 0 ? ((unsigned __int128)(nb - 1) * (unsigned long long)ldb + (unsigned)k) * 8u : 0);
-    return a && b && na > 0 && nb > 0 && a0 < b1 && b0 < a1;
-}
-
-// Device-resident index arrays are range-checked on the device (host arrays are checked on the host).
-int check_device_indices(const int *d_a, long long n, int limit, const char *what)
-{
-    if (n <= 0)
-        return SMVP_OK;
-    int *d_bad = nullptr, h_bad = 0;
-    HIP_TRY(hipMalloc((void **)&d_bad, sizeof(int)));
-    hipError_t e = hipMemset(d_bad, 0, sizeof(int));
-    if (e == hipSuccess)
-        e = smvp::launch_find_out_of_range(d_a, n, limit, d_bad, nullptr);
-    if (e == hipSuccess)
-        e = hipMemcpy(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    if (e != hipSuccess)
-        return smvp::fail(SMVP_ERR_HIP, "range check of %s failed: %s", what, hipGetErrorString(e));
-    if (h_bad)
-        return smvp::fail(SMVP_ERR_INVALID, "%s[%d] lies outside [0, %d)", what, h_bad - 1, limit);
-    return SMVP_OK;
-}
-
-}  // namespace
-
 // ===========================================================================
 // CSR
 // ===========================================================================
-// what a TJDS flavour borrows from its smvp_tjds owner (set before the tile plan is built)
-struct TjdsSource {
-    const int *pos = nullptr;
-    const int *start_pos = nullptr;
-    int num_diag = 0;
-    // the two-phase product's second phase: `val` holds the products of the first phase (written anew before every launch: no value
-    // cache, overflow entries by position), the operand is the unit vector (no x gather)
-    bool unit_operand = false;
-};
-
 // The launch plans of a CSR handle.  Each is a plain struct with one release function that frees what the struct owns and
 // resets it to its default value (the idiom of smvp::BinnedPlan / free_binned_plan); what a caller asked for and must survive
 // a re-plan -- the tile size, the value cache's threshold -- stays on the handle.
@@ -264,7 +182,9 @@ void free_spmm_plan(SpmmPlan *p)
 // the derived quantities the plans are read through
 inline bool tile_ordered(int flavor) { return flavor == smvp::kFlavorTjdsS || flavor == smvp::kFlavorTjdsH; }
 inline bool runs_on_tile_plan(int k) { return k != SMVP_CSR_KERNEL_VECTOR && k != SMVP_CSR_KERNEL_COLSWEEP && k != SMVP_CSR_KERNEL_BINNED; }
-inline int owner_flavor(const smvp_csr *h) { return h->tile.d_col16 ? smvp::kFlavorCsr16 : h->flavor; }  // what the owner kernel is launched with
+// what the owner kernel is launched with: `flavor`, but for plain CSR with 16-bit column offsets (try_column_offsets builds them
+// for plain CSR only, so for a TJDS flavour this is `flavor`)
+inline int owner_flavor(const smvp_csr *h) { return h->tile.d_col16 ? smvp::kFlavorCsr16 : h->flavor; }
 inline double csr_matrix_bytes(const smvp_csr *h) { return 12.0 * h->nnz + 4.0 * (h->rows + 1.0); }
 // rows of one strip of the column sweep: a workgroup's kSweepWaves wavefronts share rb rows, or rb * parts where every strip is cut
 // into column parts (one wavefront each); XCD-private parts run on whole strips
@@ -833,6 +753,28 @@ static int csr_create_impl(smvp_csr_t **out, int device, int rows, int cols, int
     return SMVP_OK;
 }
 
+int smvp::csr_create_tjds(smvp_csr_t **out, int device, int rows, int cols, int nnz, const int *d_row_ptr, const int *d_col_ind,
+                          const double *d_val, int flavor, const TjdsSource &src)
+{
+    return csr_create_impl(out, device, rows, cols, nnz, d_row_ptr, d_col_ind, d_val, SMVP_MEM_DEVICE, nullptr, flavor, &src);
+}
+
+bool smvp::csr_value_cache(const smvp_csr_t *h, int *min_tiles, long long *cached_entries)
+{
+    const bool on = h && tile_ordered(h->flavor);
+    if (min_tiles)
+        *min_tiles = on ? h->cache_min_tiles : 0;
+    if (cached_entries)
+        *cached_entries = on ? h->tile.cached_total : 0;
+    return on;
+}
+
+int smvp::csr_replan_value_cache(smvp_csr_t *h, int min_tiles)
+{
+    h->cache_min_tiles = min_tiles;
+    return build_tile_plan(h);
+}
+
 extern "C" int smvp_csr_create(smvp_csr_t **out, int device, int rows, int cols, int nnz,
                                const int *row_ptr, const int *col_ind, const double *val,
                                int mem_kind, const int *host_row_ptr)
@@ -946,6 +888,12 @@ int smvp::csr_spmv_repeat(smvp_csr_t *h, const double *d_x, double *d_y, void *s
     return SMVP_OK;
 }
 
+// what a launch of smvp_csr_spmv returned, as the call's result
+static int launched(hipError_t e)
+{
+    return e == hipSuccess ? (int)SMVP_OK : smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
+}
+
 // stamps: device-side timing slots of this launch (owner kernel only), or nullptr
 int smvp::csr_spmv_stamped(smvp_csr_t *h, const double *d_x, double *d_y, void *stream, unsigned long long *stamps)
 {
@@ -972,17 +920,14 @@ int smvp::csr_spmv_stamped(smvp_csr_t *h, const double *d_x, double *d_y, void *
             // (profiles/r04_binned_measured.txt, section 12; the near part first: 0.668-0.670).  Pass B waits for both.
             HIP_TRY(hipEventRecord(h->binned.ev_fork, st));
             HIP_TRY(hipStreamWaitEvent(h->binned.side, h->binned.ev_fork, 0));
-            e = smvp::launch_binned_products(h->binned.bin, d_x, h->binned.side);
-            if (e != hipSuccess)
-                return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
+            if (int rc = launched(smvp::launch_binned_products(h->binned.bin, d_x, h->binned.side)))
+                return rc;
             // From here on pass A is in flight on the side stream, reading x and writing the bins: whatever fails below, the
             // caller's stream is joined to it before the error goes back -- the caller may free x or destroy the handle next.
             int rc = SMVP_OK;
             hipError_t je = hipEventRecord(h->binned.ev_join, h->binned.side);
             if (je == hipSuccess) {
-                e = smvp::launch_near_window(h->binned.bin.nw, d_x, d_y, st);
-                if (e != hipSuccess)
-                    rc = smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
+                rc = launched(smvp::launch_near_window(h->binned.bin.nw, d_x, d_y, st));
                 je = hipStreamWaitEvent(st, h->binned.ev_join, 0);
             }
             if (je != hipSuccess) {
@@ -991,20 +936,15 @@ int smvp::csr_spmv_stamped(smvp_csr_t *h, const double *d_x, double *d_y, void *
             }
             if (rc != SMVP_OK)
                 return rc;
-            e = smvp::launch_binned_sums(h->binned.bin, d_y, st);
-            if (e != hipSuccess)
-                return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
-            return SMVP_OK;
+            return launched(smvp::launch_binned_sums(h->binned.bin, d_y, st));
         }
         if (h->binned.bin.nw.on) {
-            e = smvp::launch_near_window(h->binned.bin.nw, d_x, d_y, st);
-            if (e != hipSuccess)
-                return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
+            if (int rc = launched(smvp::launch_near_window(h->binned.bin.nw, d_x, d_y, st)))
+                return rc;
         } else if (int rc = smvp::csr_spmv_stamped(h->binned.near, d_x, d_y, stream, nullptr))
             return rc;
-        e = smvp::launch_binned_products(h->binned.bin, d_x, st);
-        if (e != hipSuccess)
-            return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
+        if (int rc = launched(smvp::launch_binned_products(h->binned.bin, d_x, st)))
+            return rc;
         e = smvp::launch_binned_sums(h->binned.bin, d_y, st);
     } else if (h->kernel == SMVP_CSR_KERNEL_COLSWEEP)
         e = smvp::launch_csr_colsweep(h->sweep.d_ptr, h->sweep.d_col, h->sweep.d_val, h->sweep.d_row, d_x, d_y, h->rows,
@@ -1022,9 +962,7 @@ int smvp::csr_spmv_stamped(smvp_csr_t *h, const double *d_x, double *d_y, void *
     } else
         e = smvp::launch_csr_stream(h->vpt, h->d_row_ptr, h->d_col_ind, h->d_val, d_x, d_y, h->tile.d_tile_row,
                                     h->tile.d_carry_row, h->tile.d_carry, h->rows, h->nnz, h->tile.ntiles, st);
-    if (e != hipSuccess)
-        return smvp::fail(SMVP_ERR_HIP, "CSR launch failed: %s", hipGetErrorString(e));
-    return SMVP_OK;
+    return launched(e);
 }
 
 extern "C" int smvp_csr_spmv(smvp_csr_t *h, const double *d_x, double *d_y, void *stream)
@@ -1038,6 +976,13 @@ int smvp::csr_stamp_slots(const smvp_csr_t *h)
     return h && h->kernel == SMVP_CSR_KERNEL_STREAM && h->tile.d_tile_row ? smvp::owner_stamp_slots(h->tile.ntiles, h->flavor) : 0;
 }
 
+std::string smvp::csr_owner_kernel_name(const smvp_csr_t *h)
+{
+    char name[64];
+    snprintf(name, sizeof name, "csr_stream_owner<%d, %d, false>", h ? h->vpt : 0, h ? owner_flavor(h) : 0);
+    return name;
+}
+
 extern "C" int smvp_csr_describe(const smvp_csr_t *h, char *kernel_name, size_t cap, double *alg_bytes)
 {
     if (!h)
@@ -1047,9 +992,8 @@ extern "C" int smvp_csr_describe(const smvp_csr_t *h, char *kernel_name, size_t 
             snprintf(kernel_name, cap, "csr_binned: csr_near_window + csr_binned_far_products<2> + csr_binned_far_sums<%d, %d, 2>", h->binned.bin.slots,
                      h->binned.bin.threads_b);
         else if (h->kernel == SMVP_CSR_KERNEL_BINNED)
-            snprintf(kernel_name, cap, "csr_binned: csr_stream_owner<%d, %d, false> + csr_binned_far_products<2> + csr_binned_far_sums<%d, %d, 2>",
-                     h->binned.near ? h->binned.near->vpt : 0, h->binned.near ? owner_flavor(h->binned.near) : 0,
-                     h->binned.bin.slots, h->binned.bin.threads_b);
+            snprintf(kernel_name, cap, "csr_binned: %s + csr_binned_far_products<2> + csr_binned_far_sums<%d, %d, 2>",
+                     smvp::csr_owner_kernel_name(h->binned.near).c_str(), h->binned.bin.slots, h->binned.bin.threads_b);
         else if (h->kernel == SMVP_CSR_KERNEL_COLSWEEP)
             if (h->sweep.parts == smvp::kSweepXcdParts)
                 snprintf(kernel_name, cap, "csr_colsweep<%d> (8 column parts, one per XCD) + sweep_combine", h->sweep.g);
@@ -1060,7 +1004,7 @@ extern "C" int smvp_csr_describe(const smvp_csr_t *h, char *kernel_name, size_t 
         else if (h->kernel == SMVP_CSR_KERNEL_VECTOR)
             snprintf(kernel_name, cap, "csr_vector_rows<%d>", h->lanes_per_row);
         else if (h->kernel == SMVP_CSR_KERNEL_STREAM)
-            snprintf(kernel_name, cap, "csr_stream_owner<%d, %d, false>", h->vpt, owner_flavor(h));
+            snprintf(kernel_name, cap, "%s", smvp::csr_owner_kernel_name(h).c_str());
         else
             snprintf(kernel_name, cap, "csr_stream_tiles<%d>", h->vpt);
     }
@@ -1092,11 +1036,11 @@ extern "C" int smvp_csr_plan_launches(const smvp_csr_t *h, int *launches)
 }
 
 // bytes of device memory the current launch plan keeps beside row_ptr / col_ind / val
-static double csr_plan_bytes(const smvp_csr_t *h)
+double smvp::csr_plan_bytes(const smvp_csr_t *h)
 {
     const double n = h->nnz, t = h->tile.ntiles;
     if (h->kernel == SMVP_CSR_KERNEL_BINNED)
-        return (double)h->binned.bin.plan_bytes + (h->binned.near ? csr_plan_bytes(h->binned.near) : 0.0);
+        return (double)h->binned.bin.plan_bytes + (h->binned.near ? smvp::csr_plan_bytes(h->binned.near) : 0.0);
     if (h->kernel == SMVP_CSR_KERNEL_COLSWEEP) {
         const bool xcd = h->sweep.parts == smvp::kSweepXcdParts;
         const int strip_rows = std::max(1, sweep_strip_rows(h->sweep));
@@ -1123,7 +1067,7 @@ extern "C" int smvp_csr_plan_info(const smvp_csr_t *h, smvp_plan_info_t *out)
     if (!h || !out)
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_plan_info: bad argument");
     out->matrix_bytes = csr_matrix_bytes(h);
-    out->plan_bytes = csr_plan_bytes(h);
+    out->plan_bytes = smvp::csr_plan_bytes(h);
     out->build_ms = h->plan_build_ms;
     return SMVP_OK;
 }
@@ -1135,12 +1079,8 @@ extern "C" int smvp_csr_spmm(smvp_csr_t *h, int k, const double *d_X, long long 
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: null handle");
     if (h->flavor != smvp::kFlavorCsr)
         return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_spmm: plain CSR handles only (this one belongs to a TJDS matrix)");
-    if (k < 1 || ldx < k || ldy < k)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: k = %d, ldx = %lld, ldy = %lld (need k >= 1, ldx >= k, ldy >= k)", k, ldx, ldy);
-    if ((h->nnz > 0 && !d_X) || (h->rows > 0 && !d_Y))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: null %s", h->rows > 0 && !d_Y ? "d_Y" : "d_X");
-    if (operands_overlap(d_X, ldx, h->cols, d_Y, ldy, h->rows, k))  // X(c, v) for c < cols, Y(r, v) for r < rows (v < k)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: the byte ranges of d_X and d_Y overlap");
+    if (int rc = check_block_operands("smvp_csr_spmm", k, d_X, ldx, h->cols, d_Y, ldy, h->rows, h->nnz))  // X(c, v), c < cols; Y(r, v), r < rows
+        return rc;
     DeviceScope on(h->device);
     hipStream_t st = (hipStream_t)stream;
     if (!h->spmm.planned) {
@@ -1276,571 +1216,3 @@ extern "C" void smvp_csr_destroy(smvp_csr_t *h)
         (void)hipFree(h->d_val);
     delete h;
 }
-
-// ===========================================================================
-// TJDS
-// ===========================================================================
-struct smvp_tjds {
-    int device = 0;
-    int rows = 0, cols = 0, nnz = 0, num_diag = 0;
-    int *d_perm = nullptr;
-    int *d_start_pos = nullptr;  // num_diag + 1 entries (+1 pad)
-    int *d_row_ind = nullptr;
-    double *d_val = nullptr;
-    bool own_perm = false, own_start_pos = false, own_row_ind = false, own_val = false;
-    std::vector<int> h_start_pos;
-
-    double *d_x_perm = nullptr;  // max(rows, cols) doubles
-    bool x_set = false;
-
-    int mode = SMVP_TJDS_MODE_ROW_GATHER;
-
-    // one-kernel product (ROW_GATHER): the entries regrouped by row -- segment bounds and TJDS positions, plus the
-    // permuted columns when the 32-bit form is used; `rg` is the owner-kernel plan over that stream (the
-    // tile-ordered form keeps its own sorted copies).  Built on first use of the mode.
-    int *d_rg_ptr = nullptr;      // rows + 1
-    int *d_rg_pos = nullptr;      // nnz, row order
-    int *d_rg_k = nullptr;        // nnz, kFlavorTjdsK only
-    smvp_csr *rg = nullptr;
-
-    // two-phase product (TWO_PHASE): per-entry products + their sum per row through the row-inverted index;
-    // built on first use of the mode
-    double *d_prod = nullptr;    // nnz doubles
-    int *d_inv_ptr = nullptr;    // rows + 1
-    int *d_inv_pos = nullptr;    // nnz: positions j grouped by row_ind[j], ascending inside a row
-    smvp_csr *inv = nullptr;     // unit-value CSR over (inv_ptr, inv_pos), x = prod
-
-    // smvp_tjds_spmm (K10, smvp_tjds_spmm.hip): the entries regrouped by row in buffers of its own (not the two plans' above: they
-    // come and go with the modes), built by the first call and kept whatever the mode is
-    int *d_mm_ptr = nullptr;     // rows + 1
-    int *d_mm_pos = nullptr;     // nnz: TJDS positions, ascending inside a row
-    int *d_mm_col = nullptr;     // nnz: the original column perm[pos - start_pos[d]]
-    int *d_mm_order = nullptr;   // rows: K7's row order
-    bool mm_planned = false;
-    double mm_build_ms = 0.0;
-
-    // launch plan (rebuilt when ref-quirks mode changes)
-    bool quirks = false;
-    int *d_plan_start_pos = nullptr;  // start_pos as the kernel should see it
-    int4 *d_work = nullptr;
-    int nwork = 0;
-    long long planned_nnz = 0;
-    double plan_build_ms = 0.0;  // host wall time of the plan builds so far (work items + the modes' plans)
-};
-
-namespace {
-
-int build_tjds_plan(smvp_tjds *h, bool quirks, int ref_num_tjdiag, int last_diag_single)
-{
-    if (h->d_plan_start_pos)
-        (void)hipFree(h->d_plan_start_pos);
-    if (h->d_work)
-        (void)hipFree(h->d_work);
-    h->d_plan_start_pos = nullptr;
-    h->d_work = nullptr;
-
-    // start_pos as the product loop sees it, plus two readable pads
-    std::vector<int> sp((size_t)h->num_diag + 3, 0);
-    for (int d = 0; d <= h->num_diag; ++d)
-        sp[(size_t)d] = h->h_start_pos[(size_t)d];
-    int diag_limit = h->num_diag;
-    if (quirks) {
-        // main-cli.c:865 + :1013: diagonals 0 .. ref_num_tjdiag inclusive;
-        // main-cli.c:951-966: terminator never written after a one-entry last
-        // diagonal, and the malloc'd array reads as zero there.
-        if (last_diag_single)
-            sp[(size_t)h->num_diag] = 0;
-        diag_limit = std::min(h->num_diag, ref_num_tjdiag + 1);
-    }
-    std::vector<int4> work;
-    long long planned = 0;
-    for (int d0 = 0; d0 < diag_limit; d0 += smvp::kTjdsDiagChunk) {
-        const int d1 = std::min(d0 + smvp::kTjdsDiagChunk, diag_limit);
-        const int width = sp[(size_t)d0 + 1] - sp[(size_t)d0];  // widest diagonal of the chunk
-        for (int k0 = 0; k0 < width; k0 += smvp::kTjdsBlock)
-            work.push_back(make_int4(k0, d0, d1, 0));
-        for (int d = d0; d < d1; ++d)
-            planned += std::max(0, sp[(size_t)d + 1] - sp[(size_t)d]);
-    }
-    if (int rc = upload(&h->d_plan_start_pos, sp))
-        return rc;
-    if (int rc = upload(&h->d_work, work))
-        return rc;
-    h->nwork = (int)work.size();
-    h->quirks = quirks;
-    h->planned_nnz = planned;
-    return SMVP_OK;
-}
-
-
-void free_row_gather(smvp_tjds *h)
-{
-    smvp_csr_destroy(h->rg);
-    h->rg = nullptr;
-    for (void *p : {(void *)h->d_rg_ptr, (void *)h->d_rg_pos, (void *)h->d_rg_k})
-        if (p)
-            (void)hipFree(p);
-    h->d_rg_ptr = h->d_rg_pos = h->d_rg_k = nullptr;
-}
-
-// How the row-gather stream names an entry: tile-ordered streams with two 16-bit words per entry -- the low half of the
-// position and slot | run hint -- plus the tiles' run tables (kFlavorTjdsH, 4 bytes of index per entry: the default); the same
-// order with the 32-bit position and a 32-bit slot | diagonal word (kFlavorTjdsS, 8 bytes; needs the diagonals to fit 21 bits);
-// or 32-bit permuted columns in row
-// order (kFlavorTjdsK).  The plan option "tjds_index" = 0 | 1 | 2 selects (smvp_set_option; the tests run all three).
-int row_gather_index(const smvp_tjds *h)
-{
-    const int e = smvp::option("tjds_index", 0);
-    const bool fits_sorted = ((long long)std::max(h->num_diag - 1, 0) >> (32 - smvp::kSlotBits)) == 0;
-    if (e == 2)
-        return smvp::kFlavorTjdsK;
-    if (e == 1 && fits_sorted)
-        return smvp::kFlavorTjdsS;
-    return smvp::kFlavorTjdsH;
-}
-
-int ensure_row_gather(smvp_tjds *h)
-{
-    if (h->rg)
-        return SMVP_OK;
-    free_row_gather(h);
-    const size_t n = (size_t)std::max(h->nnz, 4);
-    const int index = row_gather_index(h);
-    if (hipMalloc((void **)&h->d_rg_ptr, ((size_t)h->rows + 4) * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&h->d_rg_pos, n * sizeof(int)) != hipSuccess ||
-        (index == smvp::kFlavorTjdsK && hipMalloc((void **)&h->d_rg_k, n * sizeof(int)) != hipSuccess))
-        return smvp::fail(SMVP_ERR_ALLOC, "TJDS: cannot allocate the row-gather plan");
-    // the true start_pos (d_plan_start_pos may carry the ref-quirks edit)
-    if (int rc = smvp::build_row_gather_plan(h->d_row_ind, h->d_start_pos, h->num_diag, h->nnz, h->rows, h->d_rg_ptr,
-                                             h->d_rg_pos, h->d_rg_k, nullptr))
-        return rc;
-    TjdsSource src;
-    src.pos = h->d_rg_pos, src.start_pos = h->d_start_pos, src.num_diag = h->num_diag;
-    return csr_create_impl(&h->rg, h->device, h->rows, std::max(h->cols, 1), h->nnz, h->d_rg_ptr, h->d_rg_k, h->d_val,
-                           SMVP_MEM_DEVICE, nullptr, index, &src);
-}
-
-int ensure_two_phase(smvp_tjds *h)
-{
-    if (h->inv)
-        return SMVP_OK;
-    const size_t n = (size_t)std::max(h->nnz, 4);
-    if ((!h->d_prod && hipMalloc((void **)&h->d_prod, n * sizeof(double)) != hipSuccess) ||
-        (!h->d_inv_pos && hipMalloc((void **)&h->d_inv_pos, n * sizeof(int)) != hipSuccess) ||
-        (!h->d_inv_ptr && hipMalloc((void **)&h->d_inv_ptr, ((size_t)h->rows + 4) * sizeof(int)) != hipSuccess))
-        return smvp::fail(SMVP_ERR_ALLOC, "TJDS: cannot allocate the two-phase buffers");
-    if (int rc = smvp::build_row_inverse(h->d_row_ind, h->nnz, h->rows, h->d_inv_ptr, h->d_inv_pos, nullptr))
-        return rc;
-    // the second phase walks the products the way the one-kernel form walks val: every tile's entries in TJDS order (neighbouring
-    // lanes read neighbouring products), one 32-bit index word per entry, no operand (round 5; before: a unit-value CSR over the
-    // row-inverted index, every product a gather of its own: 0.83 ms on memplus x944)
-    TjdsSource src;
-    src.pos = h->d_inv_pos, src.start_pos = h->d_start_pos, src.num_diag = h->num_diag, src.unit_operand = true;
-    return csr_create_impl(&h->inv, h->device, h->rows, std::max(h->cols, 1), h->nnz, h->d_inv_ptr, nullptr, h->d_prod,
-                           SMVP_MEM_DEVICE, nullptr, smvp::kFlavorTjdsH, &src);
-}
-
-int ensure_mode_plan(smvp_tjds *h)
-{
-    switch (h->mode) {
-    case SMVP_TJDS_MODE_ROW_GATHER:
-        return ensure_row_gather(h);
-    case SMVP_TJDS_MODE_TWO_PHASE:
-        return ensure_two_phase(h);
-    default:
-        return SMVP_OK;
-    }
-}
-
-bool overwrites_y(const smvp_tjds *h) { return h->mode != SMVP_TJDS_MODE_ATOMIC && !h->quirks; }
-
-}  // namespace
-
-extern "C" int smvp_tjds_create(smvp_tjds_t **out, int device, int rows, int cols, int nnz, int num_diag,
-                                const int *perm, const int *start_pos, const int *row_ind,
-                                const double *val, int mem_kind)
-{
-    if (!out || rows < 0 || cols < 0 || nnz < 0 || num_diag < 0 || !start_pos || (cols > 0 && !perm) ||
-        (nnz > 0 && (!row_ind || !val)))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_create: bad argument");
-    if (mem_kind != SMVP_MEM_HOST && mem_kind != SMVP_MEM_DEVICE)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_create: bad mem_kind");
-    if (nnz > kMaxEntries)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_create: %d entries: shard blocks this large by rows", nnz);
-    if (int rc = usable_device(device))
-        return rc;
-    DeviceScope on(device);
-
-    smvp_tjds *h = new smvp_tjds;
-    h->device = device;
-    h->rows = rows, h->cols = cols, h->nnz = nnz, h->num_diag = num_diag;
-    h->h_start_pos.resize((size_t)num_diag + 1);
-    int rc = SMVP_OK;
-    if (mem_kind == SMVP_MEM_HOST)
-        memcpy(h->h_start_pos.data(), start_pos, sizeof(int) * ((size_t)num_diag + 1));
-    else if (hipMemcpy(h->h_start_pos.data(), start_pos, sizeof(int) * ((size_t)num_diag + 1), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = smvp::fail(SMVP_ERR_HIP, "smvp_tjds_create: cannot read start_pos back from the device");
-    if (rc == SMVP_OK) {
-        // diagonals start at 0, end at nnz, and never get longer; the first one
-        // has at most `cols` entries -- the kernel's indexing relies on all of it
-        const std::vector<int> &sp = h->h_start_pos;
-        bool ok = sp[0] == 0 && sp[(size_t)num_diag] == nnz;
-        int prev = cols;
-        for (int d = 0; d < num_diag && ok; ++d) {
-            const int len = sp[(size_t)d + 1] - sp[(size_t)d];
-            ok = len >= 1 && len <= prev;
-            prev = len;
-        }
-        if (!ok)
-            rc = smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_create: start_pos is not a valid jagged-diagonal index");
-    }
-    if (rc == SMVP_OK && mem_kind == SMVP_MEM_HOST) {
-        for (int j = 0; j < nnz && rc == SMVP_OK; ++j)
-            if (row_ind[j] < 0 || row_ind[j] >= rows)
-                rc = smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_create: row_ind[%d] = %d outside [0, %d)", j, row_ind[j], rows);
-        for (int k = 0; k < cols && rc == SMVP_OK; ++k)
-            if (perm[k] < 0 || perm[k] >= cols)
-                rc = smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_create: perm[%d] = %d outside [0, %d)", k, perm[k], cols);
-    }
-    if (rc == SMVP_OK && mem_kind == SMVP_MEM_DEVICE)
-        rc = check_device_indices(row_ind, nnz, rows, "smvp_tjds_create: row_ind");
-    if (rc == SMVP_OK && mem_kind == SMVP_MEM_DEVICE)
-        rc = check_device_indices(perm, cols, cols, "smvp_tjds_create: perm");
-    if (rc == SMVP_OK)
-        rc = to_device(&h->d_perm, perm, (size_t)cols, mem_kind, &h->own_perm);
-    if (rc == SMVP_OK)
-        rc = to_device(&h->d_start_pos, start_pos, (size_t)num_diag + 1, mem_kind, &h->own_start_pos);
-    if (rc == SMVP_OK)
-        rc = to_device(&h->d_row_ind, row_ind, (size_t)nnz, mem_kind, &h->own_row_ind);
-    if (rc == SMVP_OK)
-        rc = to_device(&h->d_val, val, (size_t)nnz, mem_kind, &h->own_val);
-    if (rc == SMVP_OK) {
-        const size_t n = (size_t)std::max(std::max(rows, cols), 1);
-        if (hipMalloc((void **)&h->d_x_perm, n * sizeof(double)) != hipSuccess ||
-            hipMemset(h->d_x_perm, 0, n * sizeof(double)) != hipSuccess)
-            rc = smvp::fail(SMVP_ERR_ALLOC, "smvp_tjds_create: cannot allocate the permuted operand");
-    }
-    const double t0 = wall_ms();
-    if (rc == SMVP_OK)
-        rc = build_tjds_plan(h, false, 0, 0);
-    if (rc == SMVP_OK)
-        rc = ensure_mode_plan(h);
-    h->plan_build_ms = wall_ms() - t0;
-    if (rc != SMVP_OK) {
-        smvp_tjds_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return SMVP_OK;
-}
-
-extern "C" int smvp_tjds_set_mode(smvp_tjds_t *h, int mode)
-{
-    if (!h || mode < SMVP_TJDS_MODE_AUTO || mode > SMVP_TJDS_MODE_ROW_GATHER)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_set_mode: bad argument");
-    DeviceScope on(h->device);
-    const int before = h->mode;
-    h->mode = mode == SMVP_TJDS_MODE_AUTO ? SMVP_TJDS_MODE_ROW_GATHER : mode;
-    const double t0 = wall_ms();
-    if (int rc = ensure_mode_plan(h)) {
-        h->mode = before;
-        return rc;
-    }
-    h->plan_build_ms += wall_ms() - t0;
-    return SMVP_OK;
-}
-
-extern "C" int smvp_tjds_set_x(smvp_tjds_t *h, const double *d_x, void *stream)
-{
-    if (!h || (h->cols > 0 && !d_x))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_set_x: bad argument");
-    DeviceScope on(h->device);
-    hipError_t e = smvp::launch_tjds_permute(h->d_perm, d_x, h->d_x_perm, h->cols, (hipStream_t)stream);
-    if (e != hipSuccess)
-        return smvp::fail(SMVP_ERR_HIP, "operand permute launch failed: %s", hipGetErrorString(e));
-    h->x_set = true;
-    return SMVP_OK;
-}
-
-extern "C" int smvp_tjds_zero_y(smvp_tjds_t *h, double *d_y, void *stream)
-{
-    if (!h || (h->rows > 0 && !d_y))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_zero_y: bad argument");
-    if (overwrites_y(h))
-        return SMVP_OK;  // the row-gather and two-phase products overwrite y
-    DeviceScope on(h->device);
-    if (h->rows > 0)
-        HIP_TRY(hipMemsetAsync(d_y, 0, sizeof(double) * (size_t)h->rows, (hipStream_t)stream));
-    return SMVP_OK;
-}
-
-int smvp::tjds_spmv_stamped(smvp_tjds_t *h, double *d_y, void *stream, unsigned long long *stamps)
-{
-    if (!h || (h->rows > 0 && !d_y))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv: bad argument");
-    if (!h->x_set)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv: call smvp_tjds_set_x first");
-    if (h->quirks && h->rows != h->cols)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "ref-quirks mode indexes the operand by row and needs a square matrix");
-    DeviceScope on(h->device);
-    if (!h->quirks && h->mode == SMVP_TJDS_MODE_ROW_GATHER)
-        return smvp::csr_spmv_stamped(h->rg, h->d_x_perm, d_y, stream, stamps);
-    if (h->mode == SMVP_TJDS_MODE_TWO_PHASE && !h->quirks) {
-        hipError_t e1 = smvp::launch_tjds_products(h->d_plan_start_pos, h->d_val, h->d_x_perm, h->d_prod, h->d_work,
-                                                   h->nwork, h->cols, (hipStream_t)stream);
-        if (e1 != hipSuccess)
-            return smvp::fail(SMVP_ERR_HIP, "TJDS products launch failed: %s", hipGetErrorString(e1));
-        return smvp_csr_spmv(h->inv, h->d_prod, d_y, stream);
-    }
-    hipError_t e = smvp::launch_tjds_scatter(h->quirks, h->d_plan_start_pos, h->d_row_ind, h->d_val, h->d_x_perm, d_y,
-                                             h->d_work, h->nwork, h->cols, (hipStream_t)stream);
-    if (e != hipSuccess)
-        return smvp::fail(SMVP_ERR_HIP, "TJDS launch failed: %s", hipGetErrorString(e));
-    return SMVP_OK;
-}
-
-extern "C" int smvp_tjds_spmv(smvp_tjds_t *h, double *d_y, void *stream)
-{
-    return smvp::tjds_spmv_stamped(h, d_y, stream, nullptr);
-}
-
-// the row-gather product (which overwrites y) through the owner kernel of `rg`, on the operand of smvp_tjds_set_x
-int smvp::tjds_stamp_slots(const smvp_tjds_t *h)
-{
-    return h && !h->quirks && h->mode == SMVP_TJDS_MODE_ROW_GATHER ? smvp::csr_stamp_slots(h->rg) : 0;
-}
-
-int smvp::tjds_repeat_grid(const smvp_tjds_t *h) { return smvp::csr_repeat_grid(h->rg); }
-
-int smvp::tjds_spmv_repeat(smvp_tjds_t *h, double *d_y, void *stream, unsigned long long *stamps, int reps, int grid, unsigned *ctl_words,
-                           bool first_of_run, unsigned long long patience)
-{
-    return smvp::csr_spmv_repeat(h->rg, h->d_x_perm, d_y, stream, stamps, reps, grid, ctl_words, first_of_run, patience);
-}
-
-extern "C" int smvp_tjds_set_ref_quirks(smvp_tjds_t *h, int enable, int ref_num_tjdiag, int last_diag_single)
-{
-    if (!h || (enable && ref_num_tjdiag < 0))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_set_ref_quirks: bad argument");
-    DeviceScope on(h->device);
-    return build_tjds_plan(h, enable != 0, ref_num_tjdiag, last_diag_single);
-}
-
-extern "C" int smvp_tjds_describe(const smvp_tjds_t *h, char *kernel_name, size_t cap, double *alg_bytes)
-{
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "null handle");
-    if (kernel_name && cap) {
-        if (h->quirks || h->mode == SMVP_TJDS_MODE_ATOMIC)
-            snprintf(kernel_name, cap, "tjds_colmajor_scatter<%s>", h->quirks ? "true" : "false");
-        else if (h->mode == SMVP_TJDS_MODE_TWO_PHASE)
-            snprintf(kernel_name, cap, "tjds_colmajor_products + csr_stream_owner<%d, %d, false>", h->inv ? h->inv->vpt : 0,
-                     h->inv ? h->inv->flavor : 0);
-        else
-            snprintf(kernel_name, cap, "csr_stream_owner<%d, %d, false>", h->rg ? h->rg->vpt : 0, h->rg ? h->rg->flavor : 0);
-    }
-    if (alg_bytes)
-        *alg_bytes = 12.0 * h->planned_nnz + 4.0 * (h->num_diag + 1.0) + 8.0 * h->cols + 8.0 * h->rows;
-    return SMVP_OK;
-}
-
-// K8: y = A^T x from the handle's own arrays (the true start_pos, not the ref-quirks edit of the plan) and the caller's x.  No plan,
-// no x_perm, nothing of the forward product's state is read or written; every argument is checked before anything is enqueued.
-extern "C" int smvp_tjds_spmv_transposed(smvp_tjds_t *h, const double *d_x, double *d_y, void *stream)
-{
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv_transposed: null handle");
-    if ((h->nnz > 0 && !d_x) || (h->cols > 0 && !d_y))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv_transposed: null %s", h->cols > 0 && !d_y ? "d_y" : "d_x");
-    if (operands_overlap(d_x, 1, h->rows, d_y, 1, h->cols, 1))  // x[0 .. rows), y[0 .. cols)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmv_transposed: the byte ranges of d_x and d_y overlap");
-    DeviceScope on(h->device);
-    const hipError_t e = smvp::launch_tjds_transposed(h->d_start_pos, h->d_row_ind, h->d_val, h->d_perm, d_x, d_y, h->cols,
-                                                      h->num_diag, (hipStream_t)stream);
-    if (e != hipSuccess)
-        return smvp::fail(SMVP_ERR_HIP, "smvp_tjds_spmv_transposed: launch failed: %s", hipGetErrorString(e));
-    return SMVP_OK;
-}
-
-extern "C" int smvp_tjds_transposed_describe(const smvp_tjds_t *h, char *kernel_name, size_t cap, double *alg_bytes)
-{
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_transposed_describe: null handle");
-    if (kernel_name && cap)
-        snprintf(kernel_name, cap, "%s", smvp::tjds_transposed_kernel_name());
-    if (alg_bytes)
-        *alg_bytes = 12.0 * h->nnz + 4.0 * (h->num_diag + 1.0) + 4.0 * h->cols + 8.0 * h->rows + 8.0 * h->cols;
-    return SMVP_OK;
-}
-
-// K9: Y = A^T X for k vectors from the handle's own arrays and the caller's X, as K8 for one: no plan, nothing of the forward
-// product's state is read or written; every argument is checked before anything is enqueued.
-extern "C" int smvp_tjds_spmm_transposed(smvp_tjds_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream)
-{
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: null handle");
-    if (k < 1 || ldx < k || ldy < k)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: k = %d, ldx = %lld, ldy = %lld (need k >= 1, ldx >= k, ldy >= k)", k,
-                          ldx, ldy);
-    if ((h->nnz > 0 && !d_X) || (h->cols > 0 && !d_Y))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: null %s", h->cols > 0 && !d_Y ? "d_Y" : "d_X");
-    if (operands_overlap(d_X, ldx, h->rows, d_Y, ldy, h->cols, k))  // X(r, v) for r < rows, Y(c, v) for c < cols (v < k)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed: the byte ranges of d_X and d_Y overlap");
-    DeviceScope on(h->device);
-    const hipError_t e = smvp::launch_tjds_spmm_transposed(h->d_start_pos, h->d_row_ind, h->d_val, h->d_perm, d_X, ldx, d_Y, ldy,
-                                                           h->cols, h->num_diag, k, (hipStream_t)stream);
-    if (e != hipSuccess)
-        return smvp::fail(SMVP_ERR_HIP, "smvp_tjds_spmm_transposed: launch failed: %s", hipGetErrorString(e));
-    return SMVP_OK;
-}
-
-extern "C" int smvp_tjds_spmm_transposed_describe(const smvp_tjds_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes)
-{
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed_describe: null handle");
-    if (k < 1)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_transposed_describe: k = %d (need k >= 1)", k);
-    if (kernel_name && cap)
-        smvp::tjds_spmm_transposed_kernel_name(k, kernel_name, cap);
-    if (alg_bytes)
-        *alg_bytes = 12.0 * h->nnz + 4.0 * (h->num_diag + 1.0) + 4.0 * h->cols + 8.0 * k * ((double)h->rows + h->cols);
-    return SMVP_OK;
-}
-
-// K10: Y = A X for k vectors from the handle's own arrays (the true start_pos, not the ref-quirks edit) through a plan of its own
-// and the caller's X: no x_perm, no mode's plan, no value cache is read or written.  Every argument is checked before anything
-// is enqueued; the first call builds the plan (and synchronises `stream`).
-extern "C" int smvp_tjds_spmm(smvp_tjds_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream)
-{
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: null handle");
-    if (k < 1 || ldx < k || ldy < k)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: k = %d, ldx = %lld, ldy = %lld (need k >= 1, ldx >= k, ldy >= k)", k, ldx, ldy);
-    if ((h->nnz > 0 && !d_X) || (h->rows > 0 && !d_Y))
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: null %s", h->rows > 0 && !d_Y ? "d_Y" : "d_X");
-    if (operands_overlap(d_X, ldx, h->cols, d_Y, ldy, h->rows, k))  // X(c, v) for c < cols, Y(r, v) for r < rows (v < k)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: the byte ranges of d_X and d_Y overlap");
-    DeviceScope on(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (!h->mm_planned) {
-        if (int rc = refuse_capture(st, "smvp_tjds_spmm: the first call on a handle builds its plan and cannot be captured "
-                                        "(call it once outside the capture)"))
-            return rc;
-        const double t0 = wall_ms();
-        const size_t n = (size_t)std::max(h->nnz, 4);  // (buffers kept from a call whose build failed are used again)
-        if ((!h->d_mm_ptr && hipMalloc((void **)&h->d_mm_ptr, ((size_t)h->rows + 4) * sizeof(int)) != hipSuccess) ||
-            (!h->d_mm_pos && hipMalloc((void **)&h->d_mm_pos, n * sizeof(int)) != hipSuccess) ||
-            (!h->d_mm_col && hipMalloc((void **)&h->d_mm_col, n * sizeof(int)) != hipSuccess) ||
-            (!h->d_mm_order && hipMalloc((void **)&h->d_mm_order, (size_t)std::max(h->rows, 4) * sizeof(int)) != hipSuccess))
-            return smvp::fail(SMVP_ERR_ALLOC, "smvp_tjds_spmm: cannot allocate the plan (%d rows, %d entries)", h->rows, h->nnz);
-        if (int rc = smvp::build_tjds_spmm_plan(h->d_row_ind, h->d_start_pos, h->d_perm, h->num_diag, h->nnz, h->rows, h->d_mm_ptr,
-                                                h->d_mm_pos, h->d_mm_col, h->d_mm_order, st))
-            return rc;
-        h->mm_planned = true;
-        h->mm_build_ms = wall_ms() - t0;
-    }
-    const hipError_t e = smvp::launch_tjds_spmm(h->d_mm_ptr, h->d_mm_pos, h->d_mm_col, h->d_val, h->d_mm_order, d_X, ldx, d_Y, ldy,
-                                                h->rows, k, st);
-    if (e != hipSuccess)
-        return smvp::fail(SMVP_ERR_HIP, "smvp_tjds_spmm: launch failed: %s", hipGetErrorString(e));
-    return SMVP_OK;
-}
-
-extern "C" int smvp_tjds_spmm_describe(const smvp_tjds_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes, smvp_plan_info_t *plan)
-{
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_describe: null handle");
-    if (k < 1)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm_describe: k = %d (need k >= 1)", k);
-    if (kernel_name && cap)
-        smvp::tjds_spmm_kernel_name(k, kernel_name, cap);
-    const double matrix = 12.0 * h->nnz + 4.0 * (h->num_diag + 1.0) + 4.0 * h->cols;
-    if (alg_bytes)
-        *alg_bytes = matrix + 8.0 * k * ((double)h->rows + h->cols);
-    if (plan) {
-        plan->matrix_bytes = matrix;
-        plan->plan_bytes = h->mm_planned ? 4.0 * (h->rows + 1.0) + 8.0 * h->nnz + 4.0 * h->rows : 0.0;
-        plan->build_ms = h->mm_planned ? h->mm_build_ms : 0.0;
-    }
-    return SMVP_OK;
-}
-
-// Which values the one-kernel product keeps a second copy of: those of val lines whose 16 entries belong to
-// `min_tiles` tiles or more (0: none -- every value is read from val itself).  Rebuilds the plan.
-extern "C" int smvp_tjds_set_value_cache(smvp_tjds_t *h, int min_tiles)
-{
-    if (!h || !h->rg || min_tiles < 0 || min_tiles > 16)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_set_value_cache: needs the row-gather plan and 0 <= min_tiles <= 16");
-    if (!tile_ordered(h->rg->flavor))
-        return min_tiles == 0 ? (int)SMVP_OK
-                              : smvp::fail(SMVP_ERR_UNSUPPORTED, "the value cache belongs to the tile-ordered TJDS stream");
-    DeviceScope on(h->device);
-    h->rg->cache_min_tiles = min_tiles;
-    return build_tile_plan(h->rg);
-}
-
-extern "C" int smvp_tjds_get_value_cache(const smvp_tjds_t *h, int *min_tiles, long long *cached_entries)
-{
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "null handle");
-    const bool on = h->rg && tile_ordered(h->rg->flavor);
-    if (min_tiles)
-        *min_tiles = on ? h->rg->cache_min_tiles : 0;
-    if (cached_entries)
-        *cached_entries = on ? h->rg->tile.cached_total : 0;
-    return SMVP_OK;
-}
-
-extern "C" int smvp_tjds_plan_info(const smvp_tjds_t *h, smvp_plan_info_t *out)
-{
-    if (!h || !out)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_plan_info: bad argument");
-    const double n = h->nnz;
-    out->matrix_bytes = 12.0 * n + 4.0 * (h->num_diag + 1.0) + 4.0 * h->cols;
-    double b = 8.0 * std::max(h->rows, h->cols);             // x_perm
-    b += 4.0 * (h->num_diag + 3.0) + 16.0 * h->nwork;        // the column-major work items (atomic / two-phase / ref-quirks)
-    if (h->rg)
-        b += 4.0 * (h->rows + 4.0) + 4.0 * n + (h->d_rg_k ? 4.0 * n : 0.0) + csr_plan_bytes(h->rg);
-    if (h->inv)
-        b += 8.0 * n + 4.0 * (h->rows + 4.0) + 4.0 * n + csr_plan_bytes(h->inv);
-    out->plan_bytes = b;
-    out->build_ms = h->plan_build_ms;
-    return SMVP_OK;
-}
-
-// tile size of the row-gather product (development knob; 256, 1024 or 2048 entries)
-extern "C" int smvp_tjds_set_tile(smvp_tjds_t *h, int entries_per_tile)
-{
-    if (!h || !h->rg)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_set_tile: the handle has no row-gather plan");
-    return smvp_csr_set_kernel(h->rg, SMVP_CSR_KERNEL_STREAM, entries_per_tile);
-}
-
-extern "C" void smvp_tjds_destroy(smvp_tjds_t *h)
-{
-    if (!h)
-        return;
-    DeviceScope on(h->device);
-    free_row_gather(h);
-    if (h->own_perm && h->d_perm)
-        (void)hipFree(h->d_perm);
-    if (h->own_start_pos && h->d_start_pos)
-        (void)hipFree(h->d_start_pos);
-    if (h->own_row_ind && h->d_row_ind)
-        (void)hipFree(h->d_row_ind);
-    if (h->own_val && h->d_val)
-        (void)hipFree(h->d_val);
-    if (h->d_x_perm)
-        (void)hipFree(h->d_x_perm);
-    if (h->d_plan_start_pos)
-        (void)hipFree(h->d_plan_start_pos);
-    if (h->d_work)
-        (void)hipFree(h->d_work);
-    smvp_csr_destroy(h->inv);
-    for (void *p : {(void *)h->d_prod, (void *)h->d_inv_ptr, (void *)h->d_inv_pos, (void *)h->d_mm_ptr, (void *)h->d_mm_pos,
-                    (void *)h->d_mm_col, (void *)h->d_mm_order})
-        if (p)
-            (void)hipFree(p);
-    delete h;
-}
-

@@ -3,7 +3,7 @@
 What this pins is state left over from one plan when the next is built.  A CSR handle goes through every ordered pair of the
 five kernel families (STREAM, STREAM_CARRY, VECTOR, COLSWEEP, BINNED) with changing parameters, two refused calls in between,
 and ends on AUTO; a TJDS handle goes through the tile sizes, the value cache and the modes for each index form of its
-row-gather stream.  After every step a fresh handle is created and configured the same way: get_kernel(), describe(),
+row-gather stream, and through ref-quirks on and off between the modes (the matrices of ref_quirks_walk.py).  After every step a fresh handle is created and configured the same way: get_kernel(), describe(),
 launches() and plan_info() (but for build_ms) are equal and the product into a guarded y has the same bits.  Once per family
 the product is also held against the oracle (parity.check_y).  smvp_csr_spmm's plan, which belongs to row_ptr alone, gives the
 same bits and reports the same bytes before and after the walk.
@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
+import ref_quirks_walk
 import smvp_toolkit_amd as sm
 from parity import check_guards, check_y, guarded_y
 from test_gpu_parity import csr_from_lengths, row_scale
@@ -195,4 +196,46 @@ def test_tjds_walk_through_tiles_value_cache_and_modes(torch, matrices, index):
             if step == 0:
                 check_y(y, ref, scale, terms)
         fresh.close()
+    T.close()
+
+
+# the work items carry both the ref-quirks flag and the copy of start_pos that TWO_PHASE's first phase reads: each is changed
+# with the other in every state
+QUIRKS_WALK = [("quirks", True), ("mode", sm.TJDS_MODE_TWO_PHASE), ("quirks", False), ("mode", sm.TJDS_MODE_ATOMIC), ("quirks", True),
+               ("mode", sm.TJDS_MODE_ROW_GATHER), ("quirks", False), ("tile", 256), ("quirks", True), ("quirks", False)]
+
+
+@pytest.mark.parametrize("index", [0, 2])
+@pytest.mark.parametrize("name", sorted(ref_quirks_walk.LONGEST_COLUMNS))
+def test_tjds_walk_through_ref_quirks_and_modes(torch, name, index):
+    """Exact operands: every product equals the oracle's -- ob.tjds_spmv with refquirks as the handle is set -- and the fresh
+    handle's bit for bit, the atomic kernel's included.  A second handle takes the walk's mode steps only: the plan bytes of the
+    two are equal before the first step and after the last, so toggling ref-quirks leaves no bytes behind and loses none."""
+    m = ref_quirks_walk.matrix(name)
+    t = sm.tjds_from_coo(m.coo, m.rows, m.cols)
+    assert t.last_diag_single == m.oracle.last_diag_single
+    dx = dev(torch, m.x)
+    setters = {"tile": "set_tile", "mode": "set_mode", "quirks": "set_ref_quirks"}
+    with sm.option("tjds_index", index):
+        T, modes_only = sm.TjdsMatrix(t), sm.TjdsMatrix(t)
+    assert T.plan_info()["plan_bytes"] == modes_only.plan_info()["plan_bytes"]
+    now = {}
+    for step, (kind, value) in enumerate(QUIRKS_WALK):
+        what = "%s, tjds_index %d, step %d: %s %d" % (name, index, step, setters[kind], value)
+        getattr(T, setters[kind])(value)
+        now[kind] = value
+        if kind == "mode":
+            modes_only.set_mode(value)
+        with sm.option("tjds_index", index):
+            fresh = sm.TjdsMatrix(t)
+        for k in ("tile", "mode", "quirks"):
+            if k in now:
+                getattr(fresh, setters[k])(now[k])
+        assert T.describe() == fresh.describe() and T.get_value_cache() == fresh.get_value_cache(), what
+        y = tjds_product(torch, T, dx)                               # (checks the guards)
+        assert_bits(y, tjds_product(torch, fresh, dx), what + " (%s), walked against fresh" % T.describe()[0])
+        assert np.array_equal(y, m.y[now["quirks"]]), what + " (%s), against the oracle" % T.describe()[0]
+        fresh.close()
+    assert T.plan_info()["plan_bytes"] == modes_only.plan_info()["plan_bytes"]
+    modes_only.close()
     T.close()

@@ -466,10 +466,10 @@ def test_transposed_invalid_arguments_write_nothing(torch):
 
 
 def inner_csr_handle(T, rows, cols, nnz):
-    """The smvp_csr_t a TJDS handle in ROW_GATHER mode keeps inside (struct smvp_tjds::rg, smvp_engine.hip).  The C ABI does
+    """The smvp_csr_t a TJDS handle in ROW_GATHER mode keeps inside (struct smvp_tjds::rg.csr, smvp_tjds.hip).  The C ABI does
     not hand it out, so it is read from the handle's memory: the x86-64 layout of the struct's head is {int device, rows,
     cols, nnz, num_diag; four pointers at 24; four bools at 56; a std::vector at 64; d_x_perm at 88; bool x_set at 96;
-    int mode at 100; three pointers at 104; rg at 128}.  Every field that can be checked is checked on both structs before
+    int mode at 100; the three pointers of rg at 104; rg.csr at 128}.  Every field that can be checked is checked on both structs before
     the pointer is used, so a layout that has moved fails here instead of passing something else on."""
     base = T._h.value
     ints = [C.c_int.from_address(base + 4 * i).value for i in range(5)]
