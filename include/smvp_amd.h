@@ -606,7 +606,9 @@ void smvp_run_opts_default(smvp_run_opts_t *o);
  * products run as ONE launch of a repeating form of the kernel whose workgroups stay resident and meet at a (fence-free: the
  * products are independent) barrier between two products; where that form is not available (or gives up: the grid must be
  * resident as a whole) the products are replayed one launch each from a hipGraph.  AUTO picks DEVICE for launches of up to 4096 workgroups of the tile
- * kernels (where an event pair would measure mostly itself: the reference's own sample matrices), else EVENTS. */
+ * kernels (where an event pair would measure mostly itself: the reference's own sample matrices), else EVENTS.  DEVICE and
+ * DEVICE_GRAPH are refused (SMVP_ERR_UNSUPPORTED) where no launch can stamp itself: any other kernel, several GPUs, a changing
+ * operand, and a matrix without rows, whose product launches nothing (AUTO times that one with events). */
 enum { SMVP_TIMING_AUTO = 0, SMVP_TIMING_EVENTS = 1, SMVP_TIMING_DEVICE = 2,
        SMVP_TIMING_DEVICE_GRAPH = 3 /* DEVICE, but one launch per product replayed from a hipGraph: what DEVICE falls back to */ };
 typedef struct smvp_run_info {

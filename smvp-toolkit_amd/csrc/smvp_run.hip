@@ -214,7 +214,7 @@ int run_timed_products(RunScratch &s, int rows, int iters, const smvp_run_opts_t
     const bool device_asked = o->timing == SMVP_TIMING_DEVICE || o->timing == SMVP_TIMING_DEVICE_GRAPH;
     const bool stamped = o->timing != SMVP_TIMING_EVENTS && !o->iterate && stamp_slots > 0 && (device_asked || stamp_slots <= kStampMaxSlots);
     if (device_asked && !stamped)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "device-side timing needs the tile kernel of one GPU and no --iterate");
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "device-side timing needs the tile kernel of one GPU, a matrix with rows and no --iterate");
     g_last_run.timing = stamped ? SMVP_TIMING_DEVICE : SMVP_TIMING_EVENTS;
     g_last_run.graph_replays = 0;
     g_last_run.repeat_launches = 0;
@@ -479,7 +479,9 @@ extern "C" int smvp_csr_compute(const smvp_coo_t *coo, int rows, int cols, int n
     // kernel that skipped a row could not hide behind a cleared (or an earlier) result.
     HIP_TRY(hipMemsetAsync(s.d_y, 0xff, sizeof(double) * (size_t)std::max(rows, 1), s.stream));
     smvp_csr_t *A = s.csr;
-    const int slots = smvp::csr_stamp_slots(A);
+    // (a matrix without rows launches nothing -- launch_csr_stream_owner returns at once -- so nobody would write the stamps that
+    // stamp_reduce reads: such a product is not stamped, AUTO times it with events and explicit device timing is refused)
+    const int slots = rows > 0 ? smvp::csr_stamp_slots(A) : 0;
     const int rgrid = slots > 0 ? smvp::csr_repeat_grid(A) : 0;  // the tile kernel's repeating form: n products per launch
     if (int rc = run_timed_products(
             s, rows, iters, o, slots, [](double *) { return (int)SMVP_OK; },
@@ -554,7 +556,7 @@ extern "C" int smvp_tjds_compute(const smvp_coo_t *coo, int rows, int cols, int 
             return rc;
     HIP_TRY(hipMemsetAsync(s.d_y, 0xff, sizeof(double) * (size_t)std::max(rows, 1), s.stream));  // NaN, as in the CSR path
     smvp_tjds_t *T = s.tjds;
-    const int slots = smvp::tjds_stamp_slots(T);
+    const int slots = rows > 0 ? smvp::tjds_stamp_slots(T) : 0;  // (no rows: nothing is launched, nothing stamped -- as in the CSR path)
     bool first = true;
     const bool iterate = o->iterate != 0;
     if (int rc = run_timed_products(

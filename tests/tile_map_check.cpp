@@ -4,8 +4,11 @@
 // launcher picks for it (CSR: up to 64 tiles per XCD turn, TJDS: up to 32), and for EVERY group 1 ... 64 on the small counts and
 // the edges, the blocks of the padded grid map one-to-one onto [0, grid) in either direction, backward is forward reversed,
 // XCD i takes backward the groups XCD 7 - i takes forward, and the blocks dispatched first take the highest round of tiles.
+// With the argument "grids" it checks nothing and prints, for every tile count 1 ... 5000, the group and the grid the launcher
+// picks for CSR and for TJDS: "ntiles group grid group grid" (tests/test_timed_runs_host.py holds its Python mirror to them).
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "smvp_tile_map.h"
@@ -57,9 +60,16 @@ static int check(int ntiles, int group)
     return 0;
 }
 
-int main()
+int main(int argc, char **argv)
 {
     const int wanted[2] = {64, 32};  // kStreamTileGroup, kTjdsTileGroup (smvp_kernels.h)
+    if (argc > 1 && strcmp(argv[1], "grids") == 0) {
+        for (int ntiles = 1; ntiles <= 5000; ++ntiles) {
+            const int g0 = smvp::tile_group_of(ntiles, wanted[0]), g1 = smvp::tile_group_of(ntiles, wanted[1]);
+            printf("%d %d %u %d %u\n", ntiles, g0, smvp::tile_grid_of(ntiles, g0), g1, smvp::tile_grid_of(ntiles, g1));
+        }
+        return 0;
+    }
     for (int ntiles = 1; ntiles <= 5000; ++ntiles) {
         for (int w : wanted) {
             const int group = smvp::tile_group_of(ntiles, w);
