@@ -490,6 +490,76 @@ int smvp_tjds_spmm(smvp_tjds_t *h, int k, const double *d_X, long long ldx, doub
 int smvp_tjds_spmm_describe(const smvp_tjds_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes, smvp_plan_info_t *plan);
 void smvp_tjds_destroy(smvp_tjds_t *h);
 
+/* -------------------------------------------------------------- the power method */
+/* The scaled (max-norm) power method on a handle the caller already holds, kernel K11 (new: the reference only multiplies; the
+ * comment at main-cli.c:401 names power iteration as the product the assignment asked for).  It is smvp_run_opts_t's iterate +
+ * normalize loop with an eigenvalue estimate, a residual and a stop rule, run on the device.  Everything below is defined through
+ * maxima, a selection by index and correctly rounded IEEE operations, so every number has one right answer whatever order the
+ * device reduces in.
+ *
+ * For a square n x n handle, step k = 1, 2, ... has the operand x_{k-1}; x_0 is the caller's start vector, or all ones.
+ *   absmax(v)    m = the largest |v_r| over the r whose v_r is not NaN, 0.0 if there is none; p = the SMALLEST r with |v_r| == m
+ *                among those, -1 if there is none.
+ *   y_k          the handle's own product of x_{k-1}: bit for bit what smvp_csr_spmv (current plan) or smvp_tjds_set_x +
+ *                smvp_tjds_spmv (current mode) gives for that operand.
+ *   p_{k-1}      the index of absmax(x_{k-1}).
+ *   lambda_k     y_k[p_{k-1}] / x_{k-1}[p_{k-1}], the correctly rounded quotient; NaN when p_{k-1} = -1.
+ *   res_k        the largest |y_k[r] - lambda_k * x_{k-1}[r]| over the r where that value is not NaN, 0.0 if there is none.  The
+ *                product is rounded, then the difference is rounded: no FMA (-ffp-contract=off, as everywhere in the library).
+ *   (m_k, p_k)   absmax(y_k).
+ *   x_k          y_k / m_k if m_k > 0, else y_k unchanged: the rule of smvp_run_opts_t.normalize, true IEEE division.  x_k is
+ *                therefore bit for bit the k-th iterate of the iterate + normalize path on the same plan.
+ * Looked steps are the k with k % check_every == 0, and k == max_steps.  Only at a looked step is a stop rule evaluated; the
+ * first that holds, in this order, is the `reason`:
+ *   1. SMVP_POWER_NONFINITE   lambda_k is NaN or +-Inf;
+ *   2. SMVP_POWER_ZERO        not (m_k > 0): the iterate vanished;
+ *   3. SMVP_POWER_CONVERGED   res_k <= (tol * |lambda_k|) * |x_{k-1}[p_{k-1}]|, evaluated in doubles in that order (tol = 0 stops
+ *                             early only on a residual of exactly 0);
+ *   4. SMVP_POWER_MAX_STEPS   k == max_steps.
+ * The reason belongs to the step the run stopped at: with check_every > 1 an iterate that vanished or went NaN at a step nobody
+ * looked at simply carries on (a zero iterate stays zero, a NaN spreads: the next looked step sees it).
+ * On every path whose product is the same from run to run -- every CSR family, TJDS ROW_GATHER and TWO_PHASE -- every reported
+ * number and every bit of x_k is a pure function of the handle's single products (tests/power_method.py restates it in numpy;
+ * tests/test_gpu_power_method.py holds the library to those bits).  The sign and payload of a NaN are unspecified. */
+enum { SMVP_POWER_CONVERGED = 0, SMVP_POWER_MAX_STEPS = 1, SMVP_POWER_ZERO = 2, SMVP_POWER_NONFINITE = 3 };
+typedef struct smvp_power_opts {
+    unsigned struct_size; /* set by smvp_power_opts_default, checked as for smvp_run_opts_t */
+    int max_steps;        /* >= 1; default 100 */
+    int check_every;      /* >= 1; default 1 */
+    double tol;           /* >= 0, finite; default 0 */
+} smvp_power_opts_t;
+void smvp_power_opts_default(smvp_power_opts_t *o);
+typedef struct smvp_power_result {
+    int steps;         /* products done */
+    int reason;        /* SMVP_POWER_* */
+    int index;         /* p_{steps-1}: where lambda was read */
+    double eigenvalue; /* lambda_steps */
+    double residual;   /* res_steps */
+    double scale;      /* m_steps */
+} smvp_power_result_t;
+/*   - d_x0: n doubles, NULL = all ones.  d_x: n doubles, receives x_steps; it may be the same pointer as d_x0 (any other overlap
+ *     is SMVP_ERR_INVALID) and is written once, at the step the run stops at.
+ *   - lambda_each / residual_each: caller-owned HOST arrays of max_steps doubles, or NULL.  Filled for the steps done, the steps
+ *     nobody looked at included (from a device-side history copied back once at the end); left untouched beyond them.
+ *   - The call returns after the work on `stream` has finished.  It allocates its workspace per call -- two vectors, the reduce
+ *     pass's partials, the history, a status block -- and frees it on every way out.  Between looked steps nothing synchronises
+ *     with the host; at a looked step the host reads the status block (48 bytes) and nothing else.  Beside the product a step is
+ *     three launches and four passes over a vector (x and y read, y read, x written), one pass more than the normalisation of
+ *     iterate + normalize: the residual's.
+ *   - SMVP_ERR_INVALID for: a NULL handle, opts or result (a NULL handle before any HIP call); a struct_size that is not this
+ *     library's; max_steps < 1, check_every < 1, tol negative, NaN or infinite; rows != cols; a NULL d_x with n > 0; a capturing
+ *     stream.  Nothing is enqueued then, d_x and *result are left untouched, and a capturing stream's capture stays valid.
+ *   - SMVP_ERR_UNSUPPORTED (likewise) for a CSR handle that is not plain CSR, and for a TJDS handle in ATOMIC mode or with
+ *     ref-quirks on: the one is not reproducible, the other no product of a changing operand (iterate refuses it too).
+ *   - n == 0: SMVP_OK, steps 0, reason SMVP_POWER_ZERO, index -1, eigenvalue NaN, residual and scale 0.
+ *   - State: a CSR handle's plan is untouched -- smvp_csr_spmv after the call gives the bits it gave before.  A TJDS handle's
+ *     permuted operand is afterwards that of the last operand, x_{steps-1}: call smvp_tjds_set_x again before the next
+ *     smvp_tjds_spmv, as after any change of x.  A handle is used by one stream at a time, as ever. */
+int smvp_csr_power_method(smvp_csr_t *h, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
+                          smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream);
+int smvp_tjds_power_method(smvp_tjds_t *h, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
+                           smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream);
+
 /* ------------------------------------------- several GPUs, one host process */
 /* New design (the reference is one CPU thread): the matrix is cut into `ngpus` row blocks balanced by entries
  * (smvp_partition_rows); GPU g holds block g -- cut again into `chunks` row chunks, each its own CSR / TJDS handle --

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <ctime>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -166,5 +167,14 @@ int tjds_repeat_grid(const smvp_tjds_t *h);
 int tjds_spmv_repeat(smvp_tjds_t *h, double *d_y, void *stream, unsigned long long *stamps, int reps, int grid, unsigned *ctl_words,
                      bool first_of_run, unsigned long long patience);
 int tjds_spmv_stamped(smvp_tjds_t *h, double *d_y, void *stream, unsigned long long *stamps);
+
+// ------------------------------------------------------------------------------------------- the power method (K11)
+// smvp_power.hip runs the steps; the handle files check what is theirs to check and hand it their product: y = A x for device
+// vectors of the handle's size, enqueued on the call's stream.  power_check_args makes no HIP call (a null handle is refused on a
+// box without a device); power_run checks the operands and the stream, then allocates, iterates and frees.
+using PowerProduct = std::function<int(const double *d_x, double *d_y)>;
+int power_check_args(const char *fn, const void *h, const smvp_power_opts_t *opts, const smvp_power_result_t *result);
+int power_run(const char *fn, int device, int rows, int cols, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
+              smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream, const PowerProduct &product);
 
 }  // namespace smvp

@@ -970,6 +970,18 @@ extern "C" int smvp_csr_spmv(smvp_csr_t *h, const double *d_x, double *d_y, void
     return smvp::csr_spmv_stamped(h, d_x, d_y, stream, nullptr);
 }
 
+// K11 on a CSR handle: the steps are smvp_power.hip's, the product is smvp_csr_spmv's on the current plan (which it leaves as it is)
+extern "C" int smvp_csr_power_method(smvp_csr_t *h, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
+                                     smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream)
+{
+    if (int rc = smvp::power_check_args("smvp_csr_power_method", h, opts, result))
+        return rc;
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_power_method: plain CSR handles only (this one belongs to a TJDS matrix)");
+    return smvp::power_run("smvp_csr_power_method", h->device, h->rows, h->cols, opts, d_x0, d_x, result, lambda_each, residual_each, stream,
+                           [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+}
+
 // the owner kernel, whose launch can time itself on the device?
 int smvp::csr_stamp_slots(const smvp_csr_t *h)
 {

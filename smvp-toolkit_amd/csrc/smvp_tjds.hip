@@ -383,6 +383,24 @@ extern "C" int smvp_tjds_spmv(smvp_tjds_t *h, double *d_y, void *stream)
     return smvp::tjds_spmv_stamped(h, d_y, stream, nullptr);
 }
 
+// K11 on a TJDS handle: the steps are smvp_power.hip's, the product is smvp_tjds_set_x + smvp_tjds_spmv in the current mode -- one
+// that overwrites y and gives the same bits on every run
+extern "C" int smvp_tjds_power_method(smvp_tjds_t *h, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
+                                      smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream)
+{
+    if (int rc = smvp::power_check_args("smvp_tjds_power_method", h, opts, result))
+        return rc;
+    if (!overwrites_y(h))
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_power_method: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
+                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
+    return smvp::power_run("smvp_tjds_power_method", h->device, h->rows, h->cols, opts, d_x0, d_x, result, lambda_each, residual_each, stream,
+                           [h, stream](const double *x, double *y) {
+                               if (int rc = smvp_tjds_set_x(h, x, stream))
+                                   return rc;
+                               return smvp_tjds_spmv(h, y, stream);
+                           });
+}
+
 // the row-gather product (which overwrites y) through the owner kernel of `rg`, on the operand of smvp_tjds_set_x
 int smvp::tjds_stamp_slots(const smvp_tjds_t *h)
 {

@@ -87,6 +87,16 @@ class ShardOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("chunks", C.c_int), ("balance", C.c_int), ("exchange", C.c_int)]
 
 
+class PowerOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("max_steps", C.c_int), ("check_every", C.c_int), ("tol", C.c_double)]
+
+
+class PowerResult(C.Structure):
+    _fields_ = [("steps", C.c_int), ("reason", C.c_int), ("index", C.c_int), ("eigenvalue", C.c_double),
+                ("residual", C.c_double), ("scale", C.c_double)]
+
+
+POWER_CONVERGED, POWER_MAX_STEPS, POWER_ZERO, POWER_NONFINITE = 0, 1, 2, 3
 GATHER_NONE, GATHER_OVERLAPPED, GATHER_AFTER = 0, 1, 2
 EXCHANGE_RCCL, EXCHANGE_COPIES, EXCHANGE_DIRECT, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGE_NAMES = {EXCHANGE_RCCL: "rccl", EXCHANGE_COPIES: "copies", EXCHANGE_DIRECT: "direct", EXCHANGE_AUTO: "auto"}
@@ -120,6 +130,7 @@ EXPORTS = [
     "smvp_csr_describe", "smvp_csr_plan_launches", "smvp_csr_destroy", "smvp_csr_spmm", "smvp_csr_spmm_describe",
     "smvp_csr_create_transposed", "smvp_csr_device_arrays", "smvp_tjds_spmv_transposed", "smvp_tjds_transposed_describe",
     "smvp_tjds_spmm_transposed", "smvp_tjds_spmm_transposed_describe", "smvp_tjds_spmm", "smvp_tjds_spmm_describe",
+    "smvp_power_opts_default", "smvp_csr_power_method", "smvp_tjds_power_method",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -167,6 +178,10 @@ def lib():
         L.smvp_tjds_spmm_transposed_describe.argtypes = [vp, ci, C.c_char_p, C.c_size_t, C.POINTER(C.c_double)]
         L.smvp_tjds_spmm.argtypes = [vp, ci, vp, C.c_longlong, vp, C.c_longlong, vp]
         L.smvp_tjds_spmm_describe.argtypes = [vp, ci, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(PlanInfo)]
+        L.smvp_power_opts_default.argtypes = [C.POINTER(PowerOpts)]
+        L.smvp_power_opts_default.restype = None
+        L.smvp_csr_power_method.argtypes = [vp, C.POINTER(PowerOpts), vp, vp, C.POINTER(PowerResult), vp, vp, vp]
+        L.smvp_tjds_power_method.argtypes = [vp, C.POINTER(PowerOpts), vp, vp, C.POINTER(PowerResult), vp, vp, vp]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -497,6 +512,24 @@ def transposed_operands(x, y, rows, cols):
             raise ValueError("%s must be contiguous; its strides are %s" % (name, tuple(t.stride())))
 
 
+def power_opts(max_steps, tol=0.0, check_every=1):
+    """smvp_power_opts_t from smvp_power_opts_default with the three fields set."""
+    o = PowerOpts()
+    lib().smvp_power_opts_default(C.byref(o))
+    o.max_steps, o.check_every, o.tol = int(max_steps), int(check_every), float(tol)
+    return o
+
+
+def _power_method(fn, handle, x0, x, max_steps, tol, check_every, stream):
+    """smvp_csr_power_method / smvp_tjds_power_method -> (PowerResult, lambda_each, residual_each), the histories cut to the
+    steps done."""
+    o = power_opts(max_steps, tol, check_every)
+    r = PowerResult()
+    lam, res = np.zeros(max(int(max_steps), 1)), np.zeros(max(int(max_steps), 1))
+    _check(getattr(lib(), fn)(handle, C.byref(o), _dev_ptr(x0), _dev_ptr(x), C.byref(r), _p(lam), _p(res), _stream_ptr(stream)), fn)
+    return r, lam[:r.steps], res[:r.steps]
+
+
 class CsrMatrix:
     """Device-resident CSR matrix (smvp_csr_t).  Arrays may be numpy (copied to HBM) or torch CUDA tensors (adopted)."""
 
@@ -559,6 +592,12 @@ class CsrMatrix:
         b = C.c_double()
         _check(lib().smvp_csr_describe(self._h, name, 256, C.byref(b)), "smvp_csr_describe")
         return name.value.decode(), b.value
+
+    def power_method(self, x0, x, max_steps, tol=0.0, check_every=1, stream=None):
+        """The scaled power method on this handle's product (smvp_csr_power_method, K11): x0 (None = ones) and x are float64 CUDA
+        tensors of `rows` elements, x receives the last iterate and may be x0.  Returns (PowerResult, lambda_each,
+        residual_each) after the work on `stream` has finished; the two histories are numpy arrays of result.steps elements."""
+        return _power_method("smvp_csr_power_method", self._h, x0, x, max_steps, tol, check_every, stream)
 
     def spmm(self, X, Y, stream=None):
         """Y = A X for k vectors at once (smvp_csr_spmm): X (cols x k) and Y (rows x k) are float64 CUDA tensors with
@@ -635,6 +674,12 @@ class TjdsMatrix:
 
     def spmv(self, y, stream=None):
         _check(lib().smvp_tjds_spmv(self._h, _dev_ptr(y), _stream_ptr(stream)), "smvp_tjds_spmv")
+
+    def power_method(self, x0, x, max_steps, tol=0.0, check_every=1, stream=None):
+        """The scaled power method on this handle's product in its current mode (smvp_tjds_power_method, K11; ROW_GATHER or
+        TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.power_method.  Afterwards the handle's permuted operand is the
+        last step's: call set_x again before the next spmv."""
+        return _power_method("smvp_tjds_power_method", self._h, x0, x, max_steps, tol, check_every, stream)
 
     def spmv_transposed(self, x, y, stream=None):
         """y = A^T x from the TJDS arrays themselves (smvp_tjds_spmv_transposed, K8): x of `rows`, y of `cols` float64 CUDA
