@@ -560,6 +560,95 @@ int smvp_csr_power_method(smvp_csr_t *h, const smvp_power_opts_t *opts, const do
 int smvp_tjds_power_method(smvp_tjds_t *h, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
                            smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream);
 
+/* ------------------------------------------------- conjugate gradients and the dot product */
+/* A x = b for a symmetric positive definite A on a handle the caller already holds, kernel K12 (new: the reference only
+ * multiplies).  Conjugate gradients need sums, and a sum has one right answer only once its order of additions is fixed.  So the
+ * order is part of this contract: with it, every number below is again a pure function of the handle's single products.
+ *
+ * dot(a, b) for n doubles.  B = 256 lanes per workgroup, G = min(ceil(n / 256), 2048) workgroups.
+ *   terms      t_i = a_i * b_i, rounded.  No FMA anywhere (-ffp-contract=off, as everywhere in the library).
+ *   lanes      lane l of workgroup g owns slot s = 256 g + l.  Its accumulator starts at +0.0 and adds t_s, t_{s + 256 G},
+ *              t_{s + 2 * 256 G}, ... in ascending order (a slot beyond n - 1 adds nothing).
+ *   fold256    of a workgroup's 256 accumulators c_0 .. c_255: inside each of the four wavefronts (64 consecutive lanes), for
+ *              h = 32, 16, 8, 4, 2, 1: c_j <- c_j + c_{j+h} for j < h; then ((w0 + w1) + w2) + w3 over the four wavefronts'
+ *              c_0.
+ *   partials   workgroup g's partial is fold256 of its accumulators.
+ *   result     fold256 of a second level, in which lane l starts at +0.0 and adds the partials l, l + 256, l + 512, ... in
+ *              ascending order.
+ *   n = 0      gives +0.0.
+ * An accumulator that starts at +0.0 never becomes -0.0, so adding +0.0 terms is the same as not adding: a restatement may pad
+ * (tests/cg_method.py is one, in numpy; tests/test_gpu_cg.py holds the library to its bits).
+ *
+ * smvp_vector_dot gives that dot of two device vectors in the HOST double `result`.  It allocates its partials, returns after the
+ * work on `stream` has finished and refuses a capturing stream.  SMVP_ERR_INVALID for n < 0, a NULL d_a or d_b with n > 0, a NULL
+ * result. */
+int smvp_vector_dot(int device, int n, const double *d_a, const double *d_b, double *result, void *stream);
+
+/* Plain conjugate gradients on a square n x n handle.  `dot` is the one above; every other operation is one correctly rounded
+ * IEEE operation per element (alpha * p_i is rounded, then the sum is rounded).
+ *   bb    = dot(b, b)            thr = (tol * tol) * bb   (tol * tol rounded on the host, the product on the device)
+ *   x_0   = d_x0, or zeros if NULL
+ *   r_0   = b - A x_0            (d_x0 == NULL: r_0 = b bit for bit, no product is run)
+ *   p_0   = r_0                  rho_0 = dot(r_0, r_0)
+ *   step 0 rule:   NONFINITE if bb or rho_0 is NaN or +-Inf;  CONVERGED if rho_0 <= thr
+ *   step k = 1, 2, ...:
+ *     q_k     = A p_{k-1}        the handle's own product, bit for bit: smvp_csr_spmv (current plan), or smvp_tjds_set_x +
+ *                                smvp_tjds_spmv (current mode)
+ *     sigma_k = dot(p_{k-1}, q_k)
+ *     rule A:   NONFINITE if sigma_k is NaN or +-Inf;  BREAKDOWN if not (sigma_k > 0)      -> x stays x_{k-1}, updates = k - 1
+ *     alpha_k = rho_{k-1} / sigma_k
+ *     x_k = x_{k-1} + alpha_k * p_{k-1}        r_k = r_{k-1} - alpha_k * q_k
+ *     rho_k   = dot(r_k, r_k)
+ *     rule B:   NONFINITE if rho_k is NaN or +-Inf;  CONVERGED if rho_k <= thr;  MAX_STEPS if k == max_steps
+ *                                                                                         -> x = x_k, updates = k
+ *     beta_k  = rho_k / rho_{k-1}              p_k = r_k + beta_k * p_{k-1}
+ * No square root is taken: the histories and the result hold squared norms.
+ * The device evaluates the rules at EVERY step; the first that holds, in the order written, is the `reason`, and from then on
+ * nothing is written to x or to the histories.  The host reads a status block at looked steps only -- step 0, every k with
+ * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, updates, reason, both histories and every bit of
+ * d_x do not depend on check_every (which decides how many products are enqueued in vain, and how often the host waits).  This is
+ * stronger than the power method's "the reason belongs to the looked step": a converged x is never iterated past.
+ * Symmetry and definiteness are the caller's contract and are not checked; SMVP_CG_BREAKDOWN is what a matrix that is visibly
+ * not positive definite gets.  Preconditioning, solvers for non-symmetric matrices and the sharded handles are out of scope. */
+enum { SMVP_CG_CONVERGED = 0, SMVP_CG_MAX_STEPS = 1, SMVP_CG_BREAKDOWN = 2, SMVP_CG_NONFINITE = 3 };
+typedef struct smvp_cg_opts {
+    unsigned struct_size; /* set by smvp_cg_opts_default, checked as for smvp_run_opts_t */
+    int max_steps;        /* >= 1; default 100 */
+    int check_every;      /* >= 1; default 10 */
+    double tol;           /* >= 0, finite; default 1e-10: stop at |r| <= tol |b| */
+} smvp_cg_opts_t;
+void smvp_cg_opts_default(smvp_cg_opts_t *o);
+typedef struct smvp_cg_result {
+    int steps;   /* products of a direction done (the one for r_0 is not counted) */
+    int updates; /* updates of x done: steps, or steps - 1 after rule A */
+    int reason;  /* SMVP_CG_* */
+    int pad;
+    double rr;   /* rho_updates */
+    double bb;   /* dot(b, b) */
+} smvp_cg_result_t;
+/*   - d_b: n doubles.  d_x0: n doubles, NULL = zeros.  d_x: n doubles; the iterates live in it, and it holds x_updates afterwards.
+ *     d_x may be the same pointer as d_x0; any other overlap of the two, and any overlap of d_b and d_x, is SMVP_ERR_INVALID.
+ *     After SMVP_ERR_HIP the content of d_x is unspecified.
+ *   - rr_each: a caller-owned HOST array of max_steps + 1 doubles, filled 0 .. updates with rho.  sigma_each: max_steps doubles,
+ *     filled 0 .. steps - 1 with sigma_1 .. sigma_steps.  Either may be NULL.  Both come from a device-side history copied back
+ *     once at the end, and are left untouched beyond the filled elements.
+ *   - The call returns after the work on `stream` has finished.  It allocates its workspace per call -- three vectors, the
+ *     partials of two dots, the histories, two status blocks -- and frees it on every way out.  Beside the product a step is three
+ *     launches and ten passes over a vector (p, q read; q, r read, r written; x, p, r read, x, p written).
+ *   - SMVP_ERR_INVALID for: a NULL handle, opts, result or d_b (before any HIP call); a struct_size that is not this library's;
+ *     max_steps < 1, check_every < 1, tol negative, NaN or infinite; rows != cols; a NULL d_x with n > 0; the overlaps above; a
+ *     capturing stream.  Nothing is enqueued then, d_x and *result are left untouched, and a capturing stream's capture stays valid.
+ *   - SMVP_ERR_UNSUPPORTED (likewise) for a CSR handle that is not plain CSR, and for a TJDS handle in ATOMIC mode or with
+ *     ref-quirks on, as for the power method.
+ *   - n == 0: SMVP_OK, steps 0, updates 0, reason SMVP_CG_CONVERGED, rr = bb = +0.0.
+ *   - State: a CSR handle's plan is untouched -- smvp_csr_spmv after the call gives the bits it gave before.  A TJDS handle's
+ *     permuted operand is afterwards that of the last direction multiplied: call smvp_tjds_set_x again before the next
+ *     smvp_tjds_spmv, as after any change of x.  A handle is used by one stream at a time, as ever. */
+int smvp_csr_cg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream);
+int smvp_tjds_cg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                 smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream);
+
 /* ------------------------------------------- several GPUs, one host process */
 /* New design (the reference is one CPU thread): the matrix is cut into `ngpus` row blocks balanced by entries
  * (smvp_partition_rows); GPU g holds block g -- cut again into `chunks` row chunks, each its own CSR / TJDS handle --

@@ -169,12 +169,19 @@ int tjds_spmv_repeat(smvp_tjds_t *h, double *d_y, void *stream, unsigned long lo
 int tjds_spmv_stamped(smvp_tjds_t *h, double *d_y, void *stream, unsigned long long *stamps);
 
 // ------------------------------------------------------------------------------------------- the power method (K11)
-// smvp_power.hip runs the steps; the handle files check what is theirs to check and hand it their product: y = A x for device
+// smvp_power.hip runs the steps; the handle files check what is theirs to check and hand it their product (HandleProduct): y = A x for device
 // vectors of the handle's size, enqueued on the call's stream.  power_check_args makes no HIP call (a null handle is refused on a
 // box without a device); power_run checks the operands and the stream, then allocates, iterates and frees.
-using PowerProduct = std::function<int(const double *d_x, double *d_y)>;
+using HandleProduct = std::function<int(const double *d_x, double *d_y)>;
 int power_check_args(const char *fn, const void *h, const smvp_power_opts_t *opts, const smvp_power_result_t *result);
 int power_run(const char *fn, int device, int rows, int cols, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
-              smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream, const PowerProduct &product);
+              smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream, const HandleProduct &product);
+
+// -------------------------------------------------------------------------------------- conjugate gradients (K12)
+// smvp_cg.hip runs the steps around the same product hook, checked and handed over by the handle files as for K11.  cg_check_args
+// makes no HIP call; cg_run checks the operands and the stream, then allocates, iterates and frees.
+int cg_check_args(const char *fn, const void *h, const smvp_cg_opts_t *opts, const smvp_cg_result_t *result, const double *d_b);
+int cg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+           smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream, const HandleProduct &product);
 
 }  // namespace smvp

@@ -982,6 +982,18 @@ extern "C" int smvp_csr_power_method(smvp_csr_t *h, const smvp_power_opts_t *opt
                            [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
 }
 
+// K12 on a CSR handle: the steps are smvp_cg.hip's, the product is smvp_csr_spmv's on the current plan (which it leaves as it is)
+extern "C" int smvp_csr_cg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                           smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream)
+{
+    if (int rc = smvp::cg_check_args("smvp_csr_cg", h, opts, result, d_b))
+        return rc;
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_cg: plain CSR handles only (this one belongs to a TJDS matrix)");
+    return smvp::cg_run("smvp_csr_cg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rr_each, sigma_each, stream,
+                        [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+}
+
 // the owner kernel, whose launch can time itself on the device?
 int smvp::csr_stamp_slots(const smvp_csr_t *h)
 {

@@ -216,7 +216,7 @@ int power_check_args(const char *fn, const void *h, const smvp_power_opts_t *o, 
 }
 
 int power_run(const char *fn, int device, int rows, int cols, const smvp_power_opts_t *o, const double *d_x0, double *d_x,
-              smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream, const PowerProduct &product)
+              smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream, const HandleProduct &product)
 {
     if (rows != cols)
         return smvp::fail(SMVP_ERR_INVALID, "%s: the power method needs a square matrix (%d x %d given)", fn, rows, cols);

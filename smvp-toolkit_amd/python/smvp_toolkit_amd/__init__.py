@@ -96,7 +96,16 @@ class PowerResult(C.Structure):
                 ("residual", C.c_double), ("scale", C.c_double)]
 
 
+class CgOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("max_steps", C.c_int), ("check_every", C.c_int), ("tol", C.c_double)]
+
+
+class CgResult(C.Structure):
+    _fields_ = [("steps", C.c_int), ("updates", C.c_int), ("reason", C.c_int), ("pad", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
+
+
 POWER_CONVERGED, POWER_MAX_STEPS, POWER_ZERO, POWER_NONFINITE = 0, 1, 2, 3
+CG_CONVERGED, CG_MAX_STEPS, CG_BREAKDOWN, CG_NONFINITE = 0, 1, 2, 3
 GATHER_NONE, GATHER_OVERLAPPED, GATHER_AFTER = 0, 1, 2
 EXCHANGE_RCCL, EXCHANGE_COPIES, EXCHANGE_DIRECT, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGE_NAMES = {EXCHANGE_RCCL: "rccl", EXCHANGE_COPIES: "copies", EXCHANGE_DIRECT: "direct", EXCHANGE_AUTO: "auto"}
@@ -131,6 +140,7 @@ EXPORTS = [
     "smvp_csr_create_transposed", "smvp_csr_device_arrays", "smvp_tjds_spmv_transposed", "smvp_tjds_transposed_describe",
     "smvp_tjds_spmm_transposed", "smvp_tjds_spmm_transposed_describe", "smvp_tjds_spmm", "smvp_tjds_spmm_describe",
     "smvp_power_opts_default", "smvp_csr_power_method", "smvp_tjds_power_method",
+    "smvp_vector_dot", "smvp_cg_opts_default", "smvp_csr_cg", "smvp_tjds_cg",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -182,6 +192,11 @@ def lib():
         L.smvp_power_opts_default.restype = None
         L.smvp_csr_power_method.argtypes = [vp, C.POINTER(PowerOpts), vp, vp, C.POINTER(PowerResult), vp, vp, vp]
         L.smvp_tjds_power_method.argtypes = [vp, C.POINTER(PowerOpts), vp, vp, C.POINTER(PowerResult), vp, vp, vp]
+        L.smvp_vector_dot.argtypes = [ci, ci, vp, vp, C.POINTER(C.c_double), vp]
+        L.smvp_cg_opts_default.argtypes = [C.POINTER(CgOpts)]
+        L.smvp_cg_opts_default.restype = None
+        L.smvp_csr_cg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, C.POINTER(CgResult), vp, vp, vp]
+        L.smvp_tjds_cg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, C.POINTER(CgResult), vp, vp, vp]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -530,6 +545,44 @@ def _power_method(fn, handle, x0, x, max_steps, tol, check_every, stream):
     return r, lam[:r.steps], res[:r.steps]
 
 
+def cg_opts(max_steps=100, tol=1e-10, check_every=10):
+    """smvp_cg_opts_t from smvp_cg_opts_default with the three fields set."""
+    o = CgOpts()
+    lib().smvp_cg_opts_default(C.byref(o))
+    o.max_steps, o.check_every, o.tol = int(max_steps), int(check_every), float(tol)
+    return o
+
+
+def _device_vectors(**named):
+    """Raises ValueError for a tensor that is not on the device (None passes): its address would mean nothing there."""
+    for name, t in named.items():
+        if t is not None and not isinstance(t, int) and not t.is_cuda:
+            raise ValueError("%s must be a device tensor" % name)
+
+
+def vector_dot(a, b, stream=None):
+    """dot(a, b) of two float64 CUDA tensors of equal length in the order of additions include/smvp_amd.h defines
+    (smvp_vector_dot): one right answer, bit for bit.  Returns a numpy float64 after the work on `stream` has finished."""
+    _device_vectors(a=a, b=b)
+    if a.numel() != b.numel() or a.numel() > 2 ** 31 - 1:
+        raise ValueError("a has %d elements, b has %d (need the same number, an int's at the most)" % (a.numel(), b.numel()))
+    out = C.c_double()
+    _check(lib().smvp_vector_dot(a.device.index or 0, a.numel(), _dev_ptr(a), _dev_ptr(b), C.byref(out), _stream_ptr(stream)),
+           "smvp_vector_dot")
+    return np.float64(out.value)
+
+
+def _cg(fn, handle, b, x, x0, max_steps, tol, check_every, stream):
+    """smvp_csr_cg / smvp_tjds_cg -> (CgResult, rr_each, sigma_each), the histories cut to the filled elements."""
+    _device_vectors(b=b, x=x, x0=x0)
+    o = cg_opts(max_steps, tol, check_every)
+    r = CgResult()
+    rr, sigma = np.zeros(max(int(max_steps), 0) + 1), np.zeros(max(int(max_steps), 1))
+    _check(getattr(lib(), fn)(handle, C.byref(o), _dev_ptr(b), _dev_ptr(x0), _dev_ptr(x), C.byref(r), _p(rr), _p(sigma),
+                              _stream_ptr(stream)), fn)
+    return r, rr[:r.updates + 1], sigma[:r.steps]
+
+
 class CsrMatrix:
     """Device-resident CSR matrix (smvp_csr_t).  Arrays may be numpy (copied to HBM) or torch CUDA tensors (adopted)."""
 
@@ -598,6 +651,13 @@ class CsrMatrix:
         tensors of `rows` elements, x receives the last iterate and may be x0.  Returns (PowerResult, lambda_each,
         residual_each) after the work on `stream` has finished; the two histories are numpy arrays of result.steps elements."""
         return _power_method("smvp_csr_power_method", self._h, x0, x, max_steps, tol, check_every, stream)
+
+    def cg(self, b, x, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Conjugate gradients for A x = b on this handle's product (smvp_csr_cg, K12; A symmetric positive definite): b, x and
+        x0 (None = zeros) are float64 CUDA tensors of `rows` elements, x receives the solution and may be x0.  Returns (CgResult,
+        rr_each, sigma_each) after the work on `stream` has finished: rr_each has result.updates + 1 squared residual norms,
+        sigma_each result.steps values of p.Ap.  Nothing depends on check_every but how often the host waits."""
+        return _cg("smvp_csr_cg", self._h, b, x, x0, max_steps, tol, check_every, stream)
 
     def spmm(self, X, Y, stream=None):
         """Y = A X for k vectors at once (smvp_csr_spmm): X (cols x k) and Y (rows x k) are float64 CUDA tensors with
@@ -680,6 +740,12 @@ class TjdsMatrix:
         TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.power_method.  Afterwards the handle's permuted operand is the
         last step's: call set_x again before the next spmv."""
         return _power_method("smvp_tjds_power_method", self._h, x0, x, max_steps, tol, check_every, stream)
+
+    def cg(self, b, x, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Conjugate gradients for A x = b on this handle's product in its current mode (smvp_tjds_cg, K12; ROW_GATHER or
+        TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.cg.  Afterwards the handle's permuted operand is the last
+        direction's: call set_x again before the next spmv."""
+        return _cg("smvp_tjds_cg", self._h, b, x, x0, max_steps, tol, check_every, stream)
 
     def spmv_transposed(self, x, y, stream=None):
         """y = A^T x from the TJDS arrays themselves (smvp_tjds_spmv_transposed, K8): x of `rows`, y of `cols` float64 CUDA
