@@ -609,7 +609,8 @@ int smvp_vector_dot(int device, int n, const double *d_a, const double *d_b, dou
  * d_x do not depend on check_every (which decides how many products are enqueued in vain, and how often the host waits).  This is
  * stronger than the power method's "the reason belongs to the looked step": a converged x is never iterated past.
  * Symmetry and definiteness are the caller's contract and are not checked; SMVP_CG_BREAKDOWN is what a matrix that is visibly
- * not positive definite gets.  Preconditioning, solvers for non-symmetric matrices and the sharded handles are out of scope. */
+ * not positive definite gets (smvp_csr_bicgstab below is for a general matrix).  Preconditioning and the sharded handles are out of
+ * scope. */
 enum { SMVP_CG_CONVERGED = 0, SMVP_CG_MAX_STEPS = 1, SMVP_CG_BREAKDOWN = 2, SMVP_CG_NONFINITE = 3 };
 typedef struct smvp_cg_opts {
     unsigned struct_size; /* set by smvp_cg_opts_default, checked as for smvp_run_opts_t */
@@ -648,6 +649,89 @@ int smvp_csr_cg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, co
                 smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream);
 int smvp_tjds_cg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                  smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream);
+
+/* ------------------------------------------------- BiCGSTAB */
+/* A x = b for a general (non-symmetric) square A on a handle the caller already holds, kernel K13 (new: the reference only
+ * multiplies).  It needs only y = A x.  `dot` is the one above, unchanged; every other operation is one correctly rounded IEEE
+ * operation per element, with no FMA (-ffp-contract=off, as everywhere in the library): with the dot's order fixed, every number
+ * below is a pure function of the handle's single products.
+ *   bb = dot(b, b)        thr = (tol * tol) * bb      (tol * tol rounded on the host, the product on the device)
+ *   x_0 = d_x0, or zeros if NULL
+ *   r_0 = b - A x_0       (d_x0 == NULL: r_0 = b bit for bit, no product is run)
+ *   rhat = r_0  (kept for the whole run)      p_0 = r_0      rho_0 = rr_0 = dot(r_0, r_0)
+ *   step 0 rule:  NONFINITE if bb or rr_0 is NaN or +-Inf;  CONVERGED if rr_0 <= thr
+ *   step k = 1, 2, ...:
+ *     v     = A p_{k-1}                      the handle's own product, bit for bit: smvp_csr_spmv (current plan), or
+ *                                            smvp_tjds_set_x + smvp_tjds_spmv (current mode)
+ *     sigma = dot(rhat, v)
+ *     rule A:  NONFINITE if sigma is NaN or +-Inf;  BREAKDOWN if sigma == 0               -> x stays x_{k-1}, half = 0
+ *     alpha = rho_{k-1} / sigma
+ *     s     = r_{k-1} - alpha * v            (alpha * v_i rounded, then the difference rounded)
+ *     ss    = dot(s, s)
+ *     rule H:  NONFINITE if ss is NaN or +-Inf                                             -> x stays x_{k-1}, half = 0
+ *              CONVERGED if ss <= thr                                                      -> x = x_{k-1} + alpha * p_{k-1}, half = 1
+ *     t     = A s                            the handle's own product
+ *     ts = dot(t, s)      tt = dot(t, t)
+ *     rule T:  NONFINITE if ts or tt is NaN or +-Inf                                       -> x stays x_{k-1}, half = 0
+ *              BREAKDOWN if not (tt > 0)                                                   -> x = x_{k-1} + alpha * p_{k-1}, half = 1
+ *     omega = ts / tt
+ *     x_k = (x_{k-1} + alpha * p_{k-1}) + omega * s      (each product rounded; the additions in this order)
+ *     r_k = s - omega * t
+ *     rr_k = dot(r_k, r_k)      rho_k = dot(rhat, r_k)
+ *     rule B (the first that holds):  NONFINITE if rr_k or rho_k is NaN or +-Inf;  CONVERGED if rr_k <= thr;
+ *              MAX_STEPS if k == max_steps;  BREAKDOWN if omega == 0 or rho_k == 0        -> x = x_k, half = 0, full = k
+ *     beta = (rho_k / rho_{k-1}) * (alpha / omega)       (two quotients rounded, then their product)
+ *     p_k  = r_k + beta * (p_{k-1} - omega * v)          (omega * v_i rounded, the difference, beta times it, the sum: four roundings)
+ * No square root is taken: the histories and the result hold squared norms.  The residual is the recurrence's, not b - A x: the
+ * two differ by rounding, and no true-residual check is made.
+ * The device evaluates the rules at EVERY step; the first that holds, in the order written, is the `reason`, and from then on
+ * nothing is written to x or to the histories.  The host reads a status block at looked steps only -- step 0, every k with
+ * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, full, half, reason, rr, both histories and every bit
+ * of d_x do not depend on check_every (which decides how many products are enqueued in vain, and how often the host waits), exactly
+ * as for conjugate gradients.
+ * Preconditioning, restarts, a true-residual check and the sharded handles are out of scope. */
+enum { SMVP_BICGSTAB_CONVERGED = 0, SMVP_BICGSTAB_MAX_STEPS = 1, SMVP_BICGSTAB_BREAKDOWN = 2, SMVP_BICGSTAB_NONFINITE = 3 };
+typedef struct smvp_bicgstab_opts {
+    unsigned struct_size; /* set by smvp_bicgstab_opts_default, checked as for smvp_cg_opts_t */
+    int max_steps;        /* >= 1; default 100 */
+    int check_every;      /* >= 1; default 10 */
+    double tol;           /* >= 0, finite; default 1e-10: stop at |r| <= tol |b| */
+} smvp_bicgstab_opts_t;
+void smvp_bicgstab_opts_default(smvp_bicgstab_opts_t *o);
+typedef struct smvp_bicgstab_result {
+    int steps;   /* the step the run stopped in (0 at step 0); up to two products per step were enqueued, the one for r_0 not counted */
+    int full;    /* complete updates of x: steps, or steps - 1 where rule A, H or T fired */
+    int half;    /* 1: d_x additionally holds the alpha * p half update of step `steps` */
+    int reason;  /* SMVP_BICGSTAB_* */
+    double rr;   /* the squared norm of the residual that belongs to d_x: ss of the last step when half = 1, else rr_full */
+    double bb;   /* dot(b, b) */
+} smvp_bicgstab_result_t;
+/*   - d_b: n doubles.  d_x0: n doubles, NULL = zeros.  d_x: n doubles; the iterates live in it, and it holds x_full (plus the half
+ *     update where half = 1) afterwards.  d_x may be the same pointer as d_x0; any other overlap of the two, and any overlap of d_b
+ *     and d_x, is SMVP_ERR_INVALID.  After SMVP_ERR_HIP the content of d_x is unspecified.
+ *   - rr_each: a caller-owned HOST array of max_steps + 1 doubles, filled 0 .. full with rr.  ss_each: max_steps doubles, filled
+ *     with ss of every step that reached rule H (the step in which rule H or T fired included, the one in which rule A fired not).
+ *     Either may be NULL.  Both come from a device-side history copied back once at the end, and are left untouched beyond the
+ *     filled elements.  (ss is never -0.0 -- an accumulator starts at +0.0 -- so a caller who needs the count of ss_each may fill
+ *     it with -0.0 first, as the Python binding does.)
+ *   - The call returns after the work on `stream` has finished.  It allocates its workspace per call -- five vectors, the partials
+ *     of six dots, four words, the histories, two status blocks -- and frees it on every way out.  Beside the two products a step
+ *     is five launches and eighteen passes over a vector: rhat, v read (sigma's partials); v, r read, s written over r with ss's
+ *     partials; t, s read (the partials of ts and tt, two accumulators per lane); x, p, s, t, rhat read, x, r written with the
+ *     partials of rr and rho; r, p, v read, p written.
+ *   - SMVP_ERR_INVALID for: a NULL handle, opts, result or d_b (before any HIP call); a struct_size that is not this library's;
+ *     max_steps < 1, check_every < 1, tol negative, NaN or infinite; rows != cols; a NULL d_x with n > 0; the overlaps above; a
+ *     capturing stream.  Nothing is enqueued then, d_x and *result are left untouched, and a capturing stream's capture stays valid.
+ *   - SMVP_ERR_UNSUPPORTED (likewise) for a CSR handle that is not plain CSR, and for a TJDS handle in ATOMIC mode or with
+ *     ref-quirks on, as for the power method.
+ *   - n == 0: SMVP_OK, steps 0, full 0, half 0, reason SMVP_BICGSTAB_CONVERGED, rr = bb = +0.0.
+ *   - State: a CSR handle's plan is untouched -- smvp_csr_spmv after the call gives the bits it gave before.  A TJDS handle's
+ *     permuted operand is afterwards that of the last vector multiplied: call smvp_tjds_set_x again before the next
+ *     smvp_tjds_spmv, as after any change of x.  A handle is used by one stream at a time, as ever. */
+int smvp_csr_bicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                      smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream);
+int smvp_tjds_bicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                       smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream);
 
 /* ------------------------------------------- several GPUs, one host process */
 /* New design (the reference is one CPU thread): the matrix is cut into `ngpus` row blocks balanced by entries

@@ -24,6 +24,7 @@
 // the stop rules at every step.  Once one has fired, cg_residual and cg_direction of every later step see `stopped` in the status
 // block, write nothing to x, r, p or the histories, and carry the block over; the host reads the block at looked steps only, and
 // only to leave the loop.  Every operation on an element is one rounded IEEE operation (-ffp-contract=off, as everywhere).
+#include "smvp_cg_common.h"
 #include "smvp_engine.h"
 #include "smvp_kernels.h"
 
@@ -35,11 +36,6 @@ namespace smvp {
 
 namespace {
 
-constexpr int kCgBlock = 256;     // four wavefronts
-constexpr int kCgGridCap = 2048;  // workgroups of every vector pass: one grid trip = 2048 * 256 elements
-constexpr int kCgTrips = 4;       // trips in flight per lane of a pass that also writes
-constexpr int kCgDotTrips = 8;    // ... of the dot's pass, which only reads
-
 // what a step leaves behind for the next step's lanes and, at a looked step, for the host
 struct CgStatus {
     double rho;   // rho_updates: the squared residual norm of the last update
@@ -50,53 +46,6 @@ struct CgStatus {
     int steps;    // products done
     int updates;  // updates of x done
 };
-
-__device__ inline bool cg_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
-// fold256 of the workgroup's 256 accumulators, in every lane; every lane calls it, and twice in a row is fine
-__device__ inline double cg_fold256(double c)
-{
-    __shared__ double s_w[kCgBlock / 64];
-#pragma unroll
-    for (int h = 32; h > 0; h >>= 1)
-        c = c + __shfl_xor(c, h, 64);  // lane 0 ends with c_j + c_{j+h} for h = 32 ... 1 (IEEE addition is commutative)
-    __syncthreads();                   // (the last call's readers are done with s_w)
-    if ((threadIdx.x & 63) == 0)
-        s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
-
-// the second level: lane l adds the partials l, l + 256, ... in ascending order, then fold256
-__device__ inline double cg_fold_parts(const double *__restrict__ parts, int nparts)
-{
-    double c = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += kCgBlock)
-        c = c + parts[i];
-    return cg_fold256(c);
-}
-
-// a lane's accumulator of a[i] * b[i] over its slots: the terms rounded, added in ascending order
-__device__ inline double cg_lane_dot(const double *__restrict__ a, const double *__restrict__ b, int n)
-{
-    const long long stride = (long long)gridDim.x * kCgBlock;
-    long long i = (long long)blockIdx.x * kCgBlock + threadIdx.x;
-    double c = 0.0;
-    for (; i + (kCgDotTrips - 1) * stride < n; i += kCgDotTrips * stride) {
-        double t[kCgDotTrips];
-#pragma unroll
-        for (int u = 0; u < kCgDotTrips; ++u)
-            t[u] = a[i + u * stride] * b[i + u * stride];
-#pragma unroll
-        for (int u = 0; u < kCgDotTrips; ++u)
-            c = c + t[u];
-    }
-    for (; i < n; i += stride) {
-        const double t = a[i] * b[i];
-        c = c + t;
-    }
-    return c;
-}
 
 __global__ __launch_bounds__(kCgBlock) void cg_dot_parts(const double *__restrict__ a, const double *__restrict__ b, int n,
                                                          double *__restrict__ parts)
@@ -266,29 +215,7 @@ __global__ __launch_bounds__(kCgBlock) void cg_direction(double *__restrict__ x,
     }
 }
 
-// a call's workspace: freed on every way out, after what the call enqueued has finished
-struct CgWork {
-    hipStream_t stream = nullptr;
-    double *vec = nullptr;    // r, p, q
-    double *small = nullptr;  // the partials of two dots, sigma's word, the histories
-    CgStatus *st = nullptr;   // two blocks, by step parity
-    CgStatus *seen = nullptr; // pinned host memory: where a looked step's block is copied to
-    ~CgWork()
-    {
-        (void)hipStreamSynchronize(stream);
-        if (seen)
-            (void)hipHostFree(seen);
-        for (void *v : {(void *)vec, (void *)small, (void *)st})
-            if (v)
-                (void)hipFree(v);
-    }
-};
-
-inline int cg_grid(int n)
-{
-    const long long want = ((long long)n + kCgBlock - 1) / kCgBlock;
-    return (int)(want < kCgGridCap ? want : kCgGridCap);
-}
+using CgWork = KrylovWork<CgStatus>;  // r, p, q; the partials of two dots, sigma's word, the histories
 
 }  // namespace
 

@@ -994,6 +994,18 @@ extern "C" int smvp_csr_cg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const doub
                         [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
 }
 
+// K13 on a CSR handle: the steps are smvp_bicgstab.hip's, both products smvp_csr_spmv's on the current plan (which they leave as it is)
+extern "C" int smvp_csr_bicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                                 smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream)
+{
+    if (int rc = smvp::bicgstab_check_args("smvp_csr_bicgstab", h, opts, result, d_b))
+        return rc;
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_bicgstab: plain CSR handles only (this one belongs to a TJDS matrix)");
+    return smvp::bicgstab_run("smvp_csr_bicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rr_each, ss_each, stream,
+                              [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+}
+
 // the owner kernel, whose launch can time itself on the device?
 int smvp::csr_stamp_slots(const smvp_csr_t *h)
 {

@@ -419,6 +419,24 @@ extern "C" int smvp_tjds_cg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const do
                         });
 }
 
+// K13 on a TJDS handle: the steps are smvp_bicgstab.hip's, both products K11's -- smvp_tjds_set_x + smvp_tjds_spmv in a mode that
+// overwrites y and gives the same bits on every run
+extern "C" int smvp_tjds_bicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                                  smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream)
+{
+    if (int rc = smvp::bicgstab_check_args("smvp_tjds_bicgstab", h, opts, result, d_b))
+        return rc;
+    if (!overwrites_y(h))
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_bicgstab: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
+                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
+    return smvp::bicgstab_run("smvp_tjds_bicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rr_each, ss_each, stream,
+                              [h, stream](const double *x, double *y) {
+                                  if (int rc = smvp_tjds_set_x(h, x, stream))
+                                      return rc;
+                                  return smvp_tjds_spmv(h, y, stream);
+                              });
+}
+
 // the row-gather product (which overwrites y) through the owner kernel of `rg`, on the operand of smvp_tjds_set_x
 int smvp::tjds_stamp_slots(const smvp_tjds_t *h)
 {

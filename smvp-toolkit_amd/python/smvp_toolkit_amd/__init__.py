@@ -104,8 +104,17 @@ class CgResult(C.Structure):
     _fields_ = [("steps", C.c_int), ("updates", C.c_int), ("reason", C.c_int), ("pad", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
 
 
+class BicgstabOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("max_steps", C.c_int), ("check_every", C.c_int), ("tol", C.c_double)]
+
+
+class BicgstabResult(C.Structure):
+    _fields_ = [("steps", C.c_int), ("full", C.c_int), ("half", C.c_int), ("reason", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
+
+
 POWER_CONVERGED, POWER_MAX_STEPS, POWER_ZERO, POWER_NONFINITE = 0, 1, 2, 3
 CG_CONVERGED, CG_MAX_STEPS, CG_BREAKDOWN, CG_NONFINITE = 0, 1, 2, 3
+BICGSTAB_CONVERGED, BICGSTAB_MAX_STEPS, BICGSTAB_BREAKDOWN, BICGSTAB_NONFINITE = 0, 1, 2, 3
 GATHER_NONE, GATHER_OVERLAPPED, GATHER_AFTER = 0, 1, 2
 EXCHANGE_RCCL, EXCHANGE_COPIES, EXCHANGE_DIRECT, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGE_NAMES = {EXCHANGE_RCCL: "rccl", EXCHANGE_COPIES: "copies", EXCHANGE_DIRECT: "direct", EXCHANGE_AUTO: "auto"}
@@ -141,6 +150,7 @@ EXPORTS = [
     "smvp_tjds_spmm_transposed", "smvp_tjds_spmm_transposed_describe", "smvp_tjds_spmm", "smvp_tjds_spmm_describe",
     "smvp_power_opts_default", "smvp_csr_power_method", "smvp_tjds_power_method",
     "smvp_vector_dot", "smvp_cg_opts_default", "smvp_csr_cg", "smvp_tjds_cg",
+    "smvp_bicgstab_opts_default", "smvp_csr_bicgstab", "smvp_tjds_bicgstab",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -197,6 +207,10 @@ def lib():
         L.smvp_cg_opts_default.restype = None
         L.smvp_csr_cg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, C.POINTER(CgResult), vp, vp, vp]
         L.smvp_tjds_cg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, C.POINTER(CgResult), vp, vp, vp]
+        L.smvp_bicgstab_opts_default.argtypes = [C.POINTER(BicgstabOpts)]
+        L.smvp_bicgstab_opts_default.restype = None
+        L.smvp_csr_bicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
+        L.smvp_tjds_bicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -583,6 +597,30 @@ def _cg(fn, handle, b, x, x0, max_steps, tol, check_every, stream):
     return r, rr[:r.updates + 1], sigma[:r.steps]
 
 
+def bicgstab_opts(max_steps=100, tol=1e-10, check_every=10):
+    """smvp_bicgstab_opts_t from smvp_bicgstab_opts_default with the three fields set."""
+    o = BicgstabOpts()
+    lib().smvp_bicgstab_opts_default(C.byref(o))
+    o.max_steps, o.check_every, o.tol = int(max_steps), int(check_every), float(tol)
+    return o
+
+
+def _bicgstab(fn, handle, b, x, x0, max_steps, tol, check_every, stream):
+    """smvp_csr_bicgstab / smvp_tjds_bicgstab -> (BicgstabResult, rr_each, ss_each), the histories cut to the filled elements.
+    ss_each has result.steps elements, one fewer where rule A ended the run: the result block does not say which, so the array
+    starts as -0.0, which no ss can be (the dot's accumulators start at +0.0), and an element left so was not filled."""
+    _device_vectors(b=b, x=x, x0=x0)
+    o = bicgstab_opts(max_steps, tol, check_every)
+    r = BicgstabResult()
+    rr, ss = np.zeros(max(int(max_steps), 0) + 1), np.full(max(int(max_steps), 1), -0.0)
+    _check(getattr(lib(), fn)(handle, C.byref(o), _dev_ptr(b), _dev_ptr(x0), _dev_ptr(x), C.byref(r), _p(rr), _p(ss),
+                              _stream_ptr(stream)), fn)
+    filled = r.steps
+    if filled > 0 and ss[filled - 1] == 0.0 and np.signbit(ss[filled - 1]):
+        filled -= 1
+    return r, rr[:r.full + 1], ss[:filled]
+
+
 class CsrMatrix:
     """Device-resident CSR matrix (smvp_csr_t).  Arrays may be numpy (copied to HBM) or torch CUDA tensors (adopted)."""
 
@@ -658,6 +696,13 @@ class CsrMatrix:
         rr_each, sigma_each) after the work on `stream` has finished: rr_each has result.updates + 1 squared residual norms,
         sigma_each result.steps values of p.Ap.  Nothing depends on check_every but how often the host waits."""
         return _cg("smvp_csr_cg", self._h, b, x, x0, max_steps, tol, check_every, stream)
+
+    def bicgstab(self, b, x, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """BiCGSTAB for A x = b on this handle's product (smvp_csr_bicgstab, K13; A any square matrix): b, x and x0 (None = zeros)
+        are float64 CUDA tensors of `rows` elements, x receives the solution and may be x0.  Returns (BicgstabResult, rr_each,
+        ss_each) after the work on `stream` has finished: rr_each has result.full + 1 squared residual norms, ss_each the squared
+        norm of s of every step that got as far.  Nothing depends on check_every but how often the host waits."""
+        return _bicgstab("smvp_csr_bicgstab", self._h, b, x, x0, max_steps, tol, check_every, stream)
 
     def spmm(self, X, Y, stream=None):
         """Y = A X for k vectors at once (smvp_csr_spmm): X (cols x k) and Y (rows x k) are float64 CUDA tensors with
@@ -746,6 +791,12 @@ class TjdsMatrix:
         TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.cg.  Afterwards the handle's permuted operand is the last
         direction's: call set_x again before the next spmv."""
         return _cg("smvp_tjds_cg", self._h, b, x, x0, max_steps, tol, check_every, stream)
+
+    def bicgstab(self, b, x, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """BiCGSTAB for A x = b on this handle's product in its current mode (smvp_tjds_bicgstab, K13; ROW_GATHER or TWO_PHASE, no
+        ref-quirks): operands and result as CsrMatrix.bicgstab.  Afterwards the handle's permuted operand is the last vector
+        multiplied: call set_x before the next spmv."""
+        return _bicgstab("smvp_tjds_bicgstab", self._h, b, x, x0, max_steps, tol, check_every, stream)
 
     def spmv_transposed(self, x, y, stream=None):
         """y = A^T x from the TJDS arrays themselves (smvp_tjds_spmv_transposed, K8): x of `rows`, y of `cols` float64 CUDA
