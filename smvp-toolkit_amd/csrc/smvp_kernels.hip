@@ -202,6 +202,20 @@ __global__ __launch_bounds__(kStreamBlock) void csr_stream_tiles(
 // longer than that are planned onto the carry kernel above instead, which
 // spreads such a row over many workgroups.
 //
+// Phase 1's lane layout (row-ordered flavours, VPT 4 and 8): neighbouring lanes take neighbouring entries.  A wavefront takes
+// 64 * VPT consecutive entries; of each 128-entry slab of them lane l has entries 2 l and 2 l + 1.  Every load is then a
+// contiguous run (double2 of val: 1 KiB per wave instruction; one 32-bit word of two 16-bit offsets: 256 B), a gather
+// instruction covers 64 entries two apart instead of 64 entries eight apart (memplus: 21.5 instead of 36.5 distinct 64-byte
+// lines of x per instruction, pwt: 11.8 instead of 20.9), and the double2 product stores go to LDS at a 16-byte lane stride.
+// Until then lane t had the 8 consecutive entries 8 t ... 8 t + 7: every lane its own 64-byte line of val, and product
+// stores at a 64-byte stride that put lanes t and t + 4 on one bank.  Measured on memplus x944, per launch
+// (profiles/tile_lane_layout_measured.txt): vector-L1 accesses 138.7 M -> 108.8 M, LDS bank-conflict cycles 28.1 M -> 5.8 M,
+// bytes unchanged, 0.2693 -> 0.2612 ms (median of seven alternated processes, every one faster than every one of the old
+// layout); pwt x459 unchanged.  The L1 count fell by 22 %, not by the factor the distinct-line count predicts: the kernel is
+// not bound by the L1's address path.  The lane-strided alternative (entry 64 k + l; 8-byte and 2-byte loads) was built and
+// measured too: 115.3 M accesses, two thirds more load instructions, headline -1.2 %, pwt x459 +2.7 % -- not merged.
+// prod[] holds every product at its row-major place whatever the layout, so phase 2 and every sum's order are untouched.
+//
 // FLAVOR selects what an "entry" is (owner_entry below):
 //   kFlavorCsr     CSR: value val[j], operand x[col_ind[j]]                       (main-cli.c:410-416)
 //   kFlavorCsr16   the same product with 10 instead of 12 bytes per entry: for the tiles whose columns span less than 65536
@@ -227,6 +241,7 @@ __global__ __launch_bounds__(kStreamBlock) void csr_stream_tiles(
 //                  gathers follow the streams after two cross-lane reads.
 // ---------------------------------------------------------------------------
 typedef int int4v __attribute__((ext_vector_type(4)));               // clang vectors: what the non-temporal builtins take
+typedef int int2v __attribute__((ext_vector_type(2)));
 
 // The streams every flavour reads are plain __restrict__ kernel parameters (the compiler then keeps the uniform plan
 // reads on the scalar unit and is free to order the loads); what only some flavours need travels in this struct.
@@ -341,7 +356,7 @@ template <int VPT, int FLAVOR, bool STAMPED>
 __device__ __forceinline__ void owner_body(
     const int *__restrict__ row_ptr, const int *__restrict__ col_ind, const double *__restrict__ val,
     const double *__restrict__ x, double *__restrict__ y, const int *__restrict__ tile_row,
-    const int *__restrict__ tile_next, int rows, int nnz_arg, int ntiles, int tile_group_arg, const OwnerExtra &ex, const int block)
+    const int *__restrict__ tile_next, int rows, int nnz_arg, int ntiles, int tile_group_arg, const OwnerExtra &ex, const int block, const int lane_salt = 0)
 {
     const OwnerArgs a = {col_ind, val, x, ex.pos, ex.start_pos, ex.ovf_val, ex.ovf_k, FLAVOR == kFlavorTjdsH ? ex.unit_x : 0};
     constexpr int TILE = kStreamBlock * VPT;
@@ -387,17 +402,26 @@ __device__ __forceinline__ void owner_body(
         SMVP_OWNER_EXIT();
     const int nnz = nnz_arg;
     const long long s = (long long)b * TILE;
-    const long long j0 = s + (long long)t * VPT;
 
     // ---- phase 1: stream + gather + multiply.  Straight-line code, ordered so that nothing waits on more
     // than one dependent round trip: the tile's own index / value loads go out first (they depend on nothing
     // but the block index), then the plan words, then row_ptr for phase 2 and the overflow entries, then ALL
     // gathers (index -> operand is the one dependence that cannot be avoided).
-    const bool whole = j0 + VPT <= (long long)nnz;  // this lane's entries all exist (always, except in the last tile)
+    // Lane layout of the row-ordered flavours (Csr, Csr16, TjdsK; the K2' block above has the reasons and the counts): a
+    // wavefront takes 64 * VPT consecutive entries of the tile in slabs of 128, and of every slab its lane l has the two
+    // entries 2 l and 2 l + 1 -- one 16-byte val load, one 4-byte word of two 16-bit offsets (8 bytes of col_ind / pos), two
+    // gathers next to its neighbours', one 16-byte LDS store at the pair's row-major place.  lane_entry(k) is the offset in
+    // the tile of this lane's entry k, for the loads, the gathers and prod[] alike.  In the last, partial tile a lane may
+    // own entries that exist and entries that do not, so EVERY lane of that tile takes the slow path, entry by entry, each
+    // tested by itself (before, only the lanes at and past the end did; the others loaded their 8 entries together).  One
+    // tile per matrix, and its longest lane is as slow as before; a matrix of one or a few tiles at VPT 4 / 8 pays it.
+    const int e0 = (t >> 6) * (64 * VPT) + (VPT > 1 ? 2 : 1) * (t & 63) + lane_salt;  // (VPT == 1: t.  lane_salt is 0: see the repeat kernel)
+    auto lane_entry = [e0](int k) { return e0 + 128 * (k >> 1) + (k & 1); };
+    const long long j0 = s + e0;  // VPT == 1: this lane's one entry
     int c[VPT];     // operand index
     int pj[VPT];    // Tjds*: position in val
     double v[VPT];
-    const bool full_tile = s + TILE <= (long long)nnz;
+    const bool full_tile = s + TILE <= (long long)nnz;  // every lane's entries exist (always, except in the last tile)
     int grp[HALF ? VPT : 1];  // TjdsH: run (inside the tile) of the first entry of this entry's group of 32
     // TjdsH: the tile's run table ({base, sub} per run), one run per lane, requested with the tile's own streams: an entry
     // then takes its run's words from its wavefront's copy by cross-lane reads instead of a second, dependent trip to memory
@@ -442,36 +466,36 @@ __device__ __forceinline__ void owner_body(
                 }
             }
         }
-    } else if (whole) {
+    } else if (full_tile) {
         if constexpr (VPT >= 4) {
+            auto load_cols = [&]() {
+#pragma unroll
+                for (int k = 0; k < VPT; k += 2)
+                    *reinterpret_cast<int2 *>(&c[k]) = *reinterpret_cast<const int2 *>(a.col_ind + s + lane_entry(k));
+            };
             if constexpr (COL16) {
                 const int base = ex.col_base[b];
                 if (base >= 0) {
 #pragma unroll
-                    for (int k = 0; k < VPT; k += 4) {  // four 16-bit offsets per 8-byte load
-                        const uint2 w = *reinterpret_cast<const uint2 *>(ex.col16 + j0 + k);
-                        c[k] = base + (int)(w.x & 0xffffu), c[k + 1] = base + (int)(w.x >> 16);
-                        c[k + 2] = base + (int)(w.y & 0xffffu), c[k + 3] = base + (int)(w.y >> 16);
+                    for (int k = 0; k < VPT; k += 2) {  // two 16-bit offsets per 4-byte load
+                        const unsigned w = *reinterpret_cast<const unsigned *>(ex.col16 + s + lane_entry(k));
+                        c[k] = base + (int)(w & 0xffffu), c[k + 1] = base + (int)(w >> 16);
                     }
                 } else {  // a tile whose columns span 65536 or more
-#pragma unroll
-                    for (int k = 0; k < VPT; k += 4)
-                        *reinterpret_cast<int4 *>(&c[k]) = *reinterpret_cast<const int4 *>(a.col_ind + j0 + k);
+                    load_cols();
                 }
             } else {
-#pragma unroll
-                for (int k = 0; k < VPT; k += 4)
-                    *reinterpret_cast<int4 *>(&c[k]) = *reinterpret_cast<const int4 *>(a.col_ind + j0 + k);
+                load_cols();
             }
             if constexpr (TJDS) {  // (read once: non-temporal)
 #pragma unroll
-                for (int k = 0; k < VPT; k += 4)
-                    *reinterpret_cast<int4v *>(&pj[k]) = __builtin_nontemporal_load(reinterpret_cast<const int4v *>(a.pos + j0 + k));
+                for (int k = 0; k < VPT; k += 2)
+                    *reinterpret_cast<int2v *>(&pj[k]) = __builtin_nontemporal_load(reinterpret_cast<const int2v *>(a.pos + s + lane_entry(k)));
             }
             if constexpr (CSR) {
 #pragma unroll
                 for (int k = 0; k < VPT; k += 2)
-                    *reinterpret_cast<double2 *>(&v[k]) = *reinterpret_cast<const double2 *>(a.val + j0 + k);
+                    *reinterpret_cast<double2 *>(&v[k]) = *reinterpret_cast<const double2 *>(a.val + s + lane_entry(k));
             }
         } else {  // VPT == 1: 256-entry tiles for matrices too small to fill the chip with 1024-entry ones
             c[0] = a.col_ind[j0];
@@ -602,7 +626,7 @@ __device__ __forceinline__ void owner_body(
             if (over0)
                 po = unit_x ? a.val[co] : vo * a.x[co];
         }
-    } else if (whole) {
+    } else if (full_tile) {
         if (rlo + t < rhi)  // this lane's first row in phase 2
             row_bounds(rlo + t, rp_a, rp_b);
         if (rlo + t + kStreamBlock < rhi)  // ... and its second: with short rows a tile holds more rows than lanes, and a row_ptr read
@@ -637,15 +661,15 @@ __device__ __forceinline__ void owner_body(
     } else {
 #pragma unroll
         for (int k = 0; k < VPT; ++k)
-            p[k] = (j0 + k < (long long)nnz) ? owner_product_slow<FLAVOR>(a, j0 + k) : 0.0;
+            p[k] = (s + lane_entry(k) < (long long)nnz) ? owner_product_slow<FLAVOR>(a, s + lane_entry(k)) : 0.0;
         if (over0)
             po = owner_product_slow<FLAVOR>(a, e + t);
     }
-    if constexpr (!SORTED) {
+    if constexpr (!SORTED) {  // every product at its row-major place
         if constexpr (VPT >= 2) {
 #pragma unroll
             for (int k = 0; k < VPT; k += 2)
-                *reinterpret_cast<double2 *>(&prod[t * VPT + k]) = make_double2(p[k], p[k + 1]);
+                *reinterpret_cast<double2 *>(&prod[lane_entry(k)]) = make_double2(p[k], p[k + 1]);
         } else {
             prod[t] = p[0];
         }
@@ -900,7 +924,13 @@ __global__ __launch_bounds__(kStreamBlock) void csr_stream_owner_repeat(
         for (int vb = (int)me; vb < ctl.grid_virtual; vb += (int)nwg) {
             if (vb != (int)me)
                 __syncthreads();  // the previous tile's LDS is free
-            owner_body<VPT, FLAVOR, false>(row_ptr, col_ind, val, x, y, tile_row, tile_next, rows, nnz_arg, ntiles, tile_group_arg, ex, vb);
+            // (a zero the compiler cannot see through, added to the lane's first entry: the per-lane stream addresses of phase 1
+            // are then formed per tile as in the single launch instead of being kept in registers across this loop -- 85-87
+            // instead of 73 registers at VPT 8, 60-62 instead of 47-50 at VPT 4, a workgroup per CU and a fifth of
+            // repeat_capacity() fewer)
+            int salt = 0;
+            asm volatile("" : "+v"(salt));
+            owner_body<VPT, FLAVOR, false>(row_ptr, col_ind, val, x, y, tile_row, tile_next, rows, nnz_arg, ntiles, tile_group_arg, ex, vb, salt);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if ((t & 63) == 0)
