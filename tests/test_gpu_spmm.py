@@ -10,6 +10,9 @@ import pytest
 
 import oracle_binding as ob
 import smvp_toolkit_amd as sm
+import special_values as sv
+import spmm_cases as sc
+import transposed as tr
 from conftest import REPORTS, SAMPLES
 from parity import G, GUARD, check_guards
 
@@ -360,3 +363,206 @@ def test_spmm_describe(torch, shaped):
     assert got.startswith("csr_spmm_rows<16> + ") and len(got) == 255
     assert alg == 12.0 * nnz + 4.0 * (M + 1) + 8.0 * (2 ** 31 - 1) * (M + M)
     A.close()
+
+
+# ------------------------------------------------------------------------------------------------------- 10. ragged rows
+ONE = "csr_spmm_rows<%d>"
+
+
+def k7(torch, rows, cols, rp, ci, val, X, ldx=None, ldy=None):
+    """A X through K7 on a fresh handle over the CSR arrays, and the oracle's serial loop on every column."""
+    k = X.shape[1]
+    A = sm.CsrMatrix(rows, cols, rp, ci, val)
+    Y = spmm(torch, A, X, k, ldx or k, ldy or k)
+    A.close()
+    with np.errstate(invalid="ignore", over="ignore"):
+        return Y, oracle(rp, ci, val, X)
+
+
+@pytest.mark.parametrize("g", sc.GROUPS)
+def test_spmm_ragged_rows_every_remainder_of_the_batch(torch, g):
+    """k = G vectors and 3 * (64 / G) + 1 rows -- three full wavefronts' worth and one row more -- whose lengths run through
+    0 ... 17: every remainder of the batch of 8, rows that end inside the first, second and third batch, empty rows, a partial last
+    wavefront; neighbouring groups of a wavefront make a different number of trips around the hand-round.  Twice, the second run
+    of lengths starting at 9, so that every length occurs for every G (13 rows at G = 16)."""
+    seen = set()
+    for start in sc.RAGGED_STARTS:
+        rows, cols, rp, ci, val, X = sc.ragged(g, start)
+        seen |= set(np.diff(rp).tolist())
+        A = sm.CsrMatrix(rows, cols, rp, ci, val)
+        assert A.spmm_describe(g)[0] == ONE % g
+        Y = spmm(torch, A, X, g, g + 1, g + 2)
+        A.close()
+        sc.assert_bits(Y, oracle(rp, ci, val, X), "G=%d rows=%d lengths from %d" % (g, rows, start))
+    assert seen == set(range(18)) and {l % sc.BATCH for l in seen} == set(range(sc.BATCH))
+
+
+def test_spmm_a_slot_past_a_rows_end_never_multiplies(torch):
+    """The last batch of a row re-reads the row's last entry in its unused slots and must leave them out (if (j + u < z)).  Every
+    value is positive and X is +Inf in the column of the last entry of every third row, in the last vector: such a row sums to
+    +Inf, and a kernel that multiplied the unused slots by 0.0 would add 0 * Inf = NaN to it.  Lengths 1 ... 17: every number of
+    unused slots."""
+    rows, cols, rp, ci, val, last_col = sc.slot_case()
+    assert {int(l) % sc.BATCH for l in np.diff(rp)[::3]} == set(range(sc.BATCH))
+    for k in (1, 2, 4, 8, 16):
+        X = sc.slot_operand(k, last_col)
+        Y, ref = k7(torch, rows, cols, rp, ci, val, X, k + 1, k + 2)
+        sc.assert_bits(Y, ref, "k = %d" % k)
+        sc.assert_slot_rows(Y, "k = %d" % k)
+
+
+# ----------------------------------------------------------------------------------------------------- 11. special values
+@pytest.mark.parametrize("name", sv.SMALL)
+def test_spmm_scenarios_a_to_d(torch, name):
+    """A: NaN / Inf in columns of X that no entry uses change no bit of Y.  B: a NaN / Inf in vector v of a used column changes
+    vector v only, and there the class of a row is the serial loop's.  C: a stored 0.0 under an Inf gives NaN.  D: rows of -0.0
+    products, zero operands and empty rows give +0.0."""
+    rows, cols, rp, ci, u = sv.structure(name)
+    o = sv.ordinary(rows, cols, rp, ci, u)
+    val = o["val"]
+    sv.assert_regime(name, "A", rows, cols, rp, ci, val, o["x_a"], u)
+    sv.assert_regime(name, "B", rows, cols, rp, ci, val, o["x_b"])
+    sv.assert_regime(name, "C", rows, cols, rp, ci, val, o["x_c"])
+    keys = ("x", "x_a", "x_b", "x", "x_c", "x_a", "x")            # 7 vectors: a pass of G = 8 with one idle lane per group
+    X = np.stack([o[key] for key in keys], axis=1)
+    Y, ref = k7(torch, rows, cols, rp, ci, val, X, 9, 8)
+    sc.assert_bits(Y, ref, name + ", A ... C")
+    clean = Y[:, 0]
+    assert np.isfinite(clean).all()
+    for c, key in enumerate(keys):
+        if key in ("x", "x_a"):                                  # unused columns poisoned, or a neighbour vector poisoned: no bit changes
+            tr.assert_bits(Y[:, c], clean, "%s: vector %d (%s) beside poisoned vectors" % (name, c, key))
+        else:
+            sv.check_classes(Y[:, c], sv.row_classes(rp, ci, val, o[key]), "%s: vector %d (%s)" % (name, c, key))
+        sv.check_no_negative_zero(Y[:, c], "%s: vector %d" % (name, c))
+    # the poisoned vector alone (k = 1) and in a pass of its own (vector 16 of 17)
+    for key in ("x_a", "x_b", "x_c"):
+        Y1, ref1 = k7(torch, rows, cols, rp, ci, val, o[key].reshape(-1, 1), 1, 1)
+        sc.assert_bits(Y1, ref1, "%s, %s alone" % (name, key))
+        X17 = np.repeat(o["x"].reshape(-1, 1), 17, axis=1)
+        X17[:, 16] = o[key]
+        Y17, ref17 = k7(torch, rows, cols, rp, ci, val, X17)
+        sc.assert_bits(Y17, ref17, "%s, %s as vector 16 of 17" % (name, key))
+        for c in range(16):
+            tr.assert_bits(Y17[:, c], clean, "%s: vector %d of 17 beside %s" % (name, c, key))
+    # D
+    for z in (np.zeros(cols), -np.zeros(cols)):
+        sv.assert_regime(name, "D", rows, cols, rp, ci, val, z)
+        Z = np.stack([z, -z, z], axis=1)
+        Yz, refz = k7(torch, rows, cols, rp, ci, val, Z, 3, 4)
+        sc.assert_bits(Yz, refz, name + ", D")
+        assert (Yz.view(np.int64) == 0).all(), "%s, D: something other than +0.0" % name
+
+
+@pytest.mark.parametrize("name", sv.SMALL)
+def test_spmm_scenarios_e_f_and_g(torch, name):
+    """E: subnormal products and sums are kept.  F: sums of +-2^1020 overflow where the serial loop's do.  G: products that round
+    -- a kernel that fuses the multiply into the add differs from the serial loop in most rows."""
+    rows, cols, rp, ci, u = sv.structure(name)
+    for scenario, (val, x) in (("E", sv.subnormal(rows, cols, rp, ci)), ("F", sv.overflowing(rows, cols, rp, ci)),
+                               ("G", sv.rounded(rows, cols, rp, ci))):
+        if scenario == "G":
+            sv.assert_regime(name, "G", rows, cols, rp, ci, val, x)
+        X = np.stack([x, -x, 0.5 * x, x, 2.0 * x if scenario != "F" else x], axis=1)     # (exact scalings: the bits follow the oracle's)
+        Y, ref = k7(torch, rows, cols, rp, ci, val, X, 6, 5)
+        if scenario == "E" and int(rp[-1]) >= 100:
+            assert np.count_nonzero(ref[:, 0]) > 0 and np.abs(ref[:, 0]).max() < 2.0 ** -1022
+        for c in range(X.shape[1]):
+            sv.assert_exact(Y[:, c], ref[:, c], "%s, %s, vector %d" % (name, scenario, c))
+
+
+# -------------------------------------------------------------------------------------- 12. row counts at the launch edges
+def test_spmm_row_counts_at_the_launch_edges(torch):
+    """Row counts around 256 / G (a workgroup), 8 * 256 / G (one round of workgroups over the XCDs) and 4096 (a sorted block) for
+    every G: a wrong `group`, a truncated last round or a block left out of the plan leaves rows NaN at some count and not at
+    others.  One fresh handle per count serves every k: its plan is built by the first call."""
+    for rows in sc.ROW_COUNTS:
+        n, cols, rp, ci, val, X = sc.row_count_case(rows)
+        ref = oracle(rp, ci, val, X)
+        A = sm.CsrMatrix(rows, cols, rp, ci, val)
+        for k in sc.ROW_COUNT_KS:
+            sc.assert_bits(spmm(torch, A, X, k, k + 1, k + 2), ref[:, :k], "%d rows, k = %d" % (rows, k))
+        A.close()
+
+
+# --------------------------------------------------------------------------------------------------------------- 13. fuzz
+@pytest.mark.parametrize("seed", sc.FUZZ_SEEDS)
+def test_spmm_fuzz_random_shapes_k_and_leading_dimensions(torch, seed):
+    """Random shapes across up to four sorted blocks, every style of row lengths, k = 1 ... 40 and padded leading dimensions:
+    the serial loop's bits on every column, and the same bits from a second call on the same handle (the plan built by the
+    first)."""
+    rows, cols, rp, ci, val, k, ldx, ldy, X = sc.block_fuzz(seed)
+    what = "fuzz %d: %d x %d, k=%d ldx=%d ldy=%d" % (seed, rows, cols, k, ldx, ldy)
+    A = sm.CsrMatrix(rows, cols, rp, ci, val)
+    first = spmm(torch, A, X, k, ldx, ldy)
+    second = spmm(torch, A, X, k, ldx, ldy)
+    A.close()
+    sc.assert_bits(first, oracle(rp, ci, val, X), what)
+    sc.assert_bits(second, first, what + ", second call")
+
+
+# ------------------------------------------------------------------------------------------ 14. offsets past 2^32 elements
+def test_spmm_offsets_into_x_and_y_beyond_2_32_elements(torch):
+    """(long long)c * ldx and (long long)r * ldy at or past 2^32 elements: 2^22 columns (then rows) with a leading dimension of
+    1030 are 2^32 + 2^24.6 elements, 34.6 GB -- the smallest operand with such an offset -- so the operands take turns: first a
+    wide X under a matrix of 100 rows, then, X freed, a tall Y over a matrix of 100 columns.  k = 3 as a slice of the wide
+    array.  Offsets kept in 32 bits, signed or unsigned, read or write somewhere else."""
+    n = 1 << 22
+    k, ld = 3, 1030
+    first_past = -(-2 ** 32 // ld)                                  # the first index whose offset no longer fits 32 bits
+    assert first_past < n - 1000
+    rng = np.random.default_rng(72)
+    # X: 100 rows of about 50 entries; a tenth of the entries past 2^32 / ld, one in the last column
+    rows, per_row = 100, 50
+    lists = []
+    for r in range(rows):
+        c = np.concatenate([rng.integers(0, n, per_row - 5), rng.integers(first_past, n, 5)])
+        lists.append(np.unique(np.append(c, n - 1) if r == rows - 1 else c))
+    rp, ci, val = csr_of(rows, n, lists, rng)
+    c64 = ci.astype(np.int64)
+    assert 4500 < len(ci) <= 5100 and (c64 > 1 << 21).sum() > 2000 and (c64 * ld >= 2 ** 31).sum() > 2000
+    assert (c64 * ld >= 2 ** 32).sum() > 300 and c64.max() == n - 1
+    Xh = rng.standard_normal((n, k))
+    ref = oracle(rp, ci, val, Xh)
+    A = sm.CsrMatrix(rows, n, rp, ci, val)
+    Xfull = torch.full((n, ld), float("nan"), dtype=torch.float64, device="cuda")
+    Xfull[:, :k] = torch.from_numpy(Xh)
+    buf, Y = guarded_Y(torch, rows, k, k + 2)
+    A.spmm(Xfull[:, :k], Y)
+    torch.cuda.synchronize()
+    A.close()
+    del Xfull
+    torch.cuda.empty_cache()
+    check_Y_guards(buf, rows, k, k + 2)
+    sc.assert_bits(Y.cpu().numpy(), ref, "X of 2^22 x 1030")
+    del buf, Y
+    # Y: 2^22 rows of 100 columns; some 20 000 rows hold entries, half of them past 2^21, more than 50 past 2^32 / ld
+    cols = 100
+    used = np.unique(np.concatenate([rng.choice(n, 20000, replace=False), [0, n - 1, (1 << 21) - 1, 1 << 21]]))
+    r = np.concatenate([used, rng.choice(used, 80000)])
+    c = rng.integers(0, cols, len(r))
+    rp, ci, val = sm.csr_from_coo(sm.make_coo(r, c, rng.uniform(-1, 1, len(r))), n)
+    assert (used > 1 << 21).sum() > 5000 and (used.astype(np.int64) * ld >= 2 ** 32).sum() > 50
+    assert set(np.flatnonzero(np.diff(rp)).tolist()) == set(used.tolist()) and rp[-1] == len(r)
+    Xh = rng.standard_normal((cols, k))
+    ref = oracle(rp, ci, val, Xh)
+    A = sm.CsrMatrix(n, cols, rp, ci, val)
+    dX = dev_X(torch, Xh, k + 1)
+    buf = torch.empty(n * ld + 2 * G, dtype=torch.float64, device="cuda")
+    buf.view(torch.int64).fill_(int(GUARD))
+    Yfull = buf[G:G + n * ld].view(n, ld)
+    Y = Yfull[:, :k]
+    Y.fill_(float("nan"))
+    A.spmm(dX, Y)
+    torch.cuda.synchronize()
+    bits = buf.view(torch.int64)
+    assert bool((bits[:G] == int(GUARD)).all()) and bool((bits[-G:] == int(GUARD)).all()), "wrote outside Y"
+    for c0 in range(k, ld, 128):                                     # (in slabs: a mask of the whole block would be 4 GB)
+        assert bool((Yfull[:, c0:c0 + 128].view(torch.int64) == int(GUARD)).all()), "a padding column k <= v < ldy was written"
+    got = Y.cpu().numpy()
+    A.close()
+    del buf, bits, Yfull, Y
+    torch.cuda.empty_cache()
+    sc.assert_bits(got[used], ref[used], "rows that hold entries")
+    assert (np.delete(got, used, axis=0).view(np.int64) == 0).all(), "a row without entries is not +0.0"
+    sc.assert_bits(got, ref, "every row")

@@ -14,6 +14,7 @@ import adopted as ad
 import oracle_binding as ob
 import smvp_toolkit_amd as sm
 import special_values as sv
+import spmm_cases as sc
 import transposed as tr
 from conftest import SAMPLES
 from parity import G, GUARD, check_guards, guarded_y
@@ -560,3 +561,36 @@ def test_k10_offsets_into_x_and_y_beyond_2_31_elements(torch):
     assert_block(got[used], ref[used], "rows that hold entries")
     assert (np.delete(got, used, axis=0).view(np.int64) == 0).all(), "a row without entries is not +0.0"
     assert_block(got, ref, "every row")
+
+
+# -------------------------------------------------------------------------------------- 14. row counts at the launch edges
+def test_k10_row_counts_at_the_launch_edges(torch):
+    """K7's launch arithmetic is K10's: row counts around 256 / G (a workgroup), 8 * 256 / G (one round of workgroups over the
+    XCDs) and 4096 (a sorted block) for every G, the entries of spmm_cases.row_count_case in a shuffled storage order.  A wrong
+    `group`, a truncated last round or a block left out of the plan leaves rows NaN at some count and not at others.  One fresh
+    handle per count serves every k: its plan is built by the first call."""
+    for rows in sc.ROW_COUNTS:
+        n, cols, rp, ci, val, X = sc.row_count_case(rows)
+        t = sm.tjds_from_coo(shuffled(tr.coo_of_csr(rp, ci, val), rows), rows, cols)
+        ref = reference_block(t, X)
+        T = sm.TjdsMatrix(t)
+        for k in sc.ROW_COUNT_KS:
+            assert_block(k10(torch, T, X[:, :k], k + 1, k + 2), ref[:, :k], "%d rows, k = %d" % (rows, k))
+        T.close()
+
+
+# --------------------------------------------------------------------------------------------------------------- 15. fuzz
+@pytest.mark.parametrize("seed", sc.FUZZ_SEEDS)
+def test_k10_fuzz_random_shapes_k_and_leading_dimensions(torch, seed):
+    """Random shapes across up to four sorted blocks, every style of row lengths, k = 1 ... 40 and padded leading dimensions,
+    the entries in a shuffled storage order: the serial TJDS loop's bits on every column, and the same bits from a second call
+    on the same handle (the plan built by the first)."""
+    rows, cols, rp, ci, val, k, ldx, ldy, X = sc.block_fuzz(seed)
+    what = "fuzz %d: %d x %d, k=%d ldx=%d ldy=%d" % (seed, rows, cols, k, ldx, ldy)
+    t = sm.tjds_from_coo(shuffled(tr.coo_of_csr(rp, ci, val), seed), rows, cols)
+    T = sm.TjdsMatrix(t)
+    first = k10(torch, T, X, ldx, ldy)
+    second = k10(torch, T, X, ldx, ldy)
+    T.close()
+    assert_block(first, reference_block(t, X), what)
+    assert_block(second, first, what + ", second call")
