@@ -609,8 +609,8 @@ int smvp_vector_dot(int device, int n, const double *d_a, const double *d_b, dou
  * d_x do not depend on check_every (which decides how many products are enqueued in vain, and how often the host waits).  This is
  * stronger than the power method's "the reason belongs to the looked step": a converged x is never iterated past.
  * Symmetry and definiteness are the caller's contract and are not checked; SMVP_CG_BREAKDOWN is what a matrix that is visibly
- * not positive definite gets (smvp_csr_bicgstab below is for a general matrix).  Preconditioning and the sharded handles are out of
- * scope. */
+ * not positive definite gets (smvp_csr_bicgstab below is for a general matrix).  A diagonal preconditioner: smvp_csr_pcg below.  The
+ * sharded handles are out of scope. */
 enum { SMVP_CG_CONVERGED = 0, SMVP_CG_MAX_STEPS = 1, SMVP_CG_BREAKDOWN = 2, SMVP_CG_NONFINITE = 3 };
 typedef struct smvp_cg_opts {
     unsigned struct_size; /* set by smvp_cg_opts_default, checked as for smvp_run_opts_t */
@@ -649,6 +649,85 @@ int smvp_csr_cg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, co
                 smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream);
 int smvp_tjds_cg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                  smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream);
+
+/* ------------------------------------------------- the diagonal of a handle */
+/* d_diag[i], i = 0 .. rows - 1, from the handle's own arrays, kernel K14 (new: the reference only ever multiplies).  Every one of
+ * the `rows` doubles is written.  Element i starts at +0.0 and adds every stored entry (i, i) in ascending storage position: for
+ * CSR the position inside the row (columns need not be sorted: the whole row is examined), for TJDS the TJDS position inside the
+ * column.  So an absent diagonal reads +0.0, a lone stored -0.0 reads +0.0 (as smvp_csr_spmv's y never holds -0.0), and repeated
+ * diagonal entries add up in storage order; both formats give the same bits for the same entries in the same order.  An element
+ * i >= cols is +0.0.  On a handle of smvp_csr_create_block the diagonal of local row r lies at global column first_row + r.
+ *   - Asynchronous on `stream`.  The calls neither allocate nor synchronise, need no plan and no smvp_tjds_set_x, can be captured
+ *     from the first call on, and leave the handle's state alone: a product afterwards gives the bits it gave before.
+ *   - `val` is read in place: adopted values changed in place are seen by the next call.
+ *   - No atomics: the same bits on every run.  Only the index array is streamed; `val` is read at the matches.
+ *   - SMVP_ERR_INVALID for a NULL handle, and for a NULL d_diag with rows > 0; SMVP_ERR_UNSUPPORTED for a smvp_csr_t that is not
+ *     plain CSR (the inner handles of a TJDS matrix), as for the solvers.  Nothing is enqueued then. */
+int smvp_csr_diagonal(const smvp_csr_t *h, double *d_diag, void *stream);
+int smvp_tjds_diagonal(const smvp_tjds_t *h, double *d_diag, void *stream);
+
+/* ------------------------------------------------- conjugate gradients with a diagonal preconditioner */
+/* Conjugate gradients on a square n x n handle, preconditioned with M = diag(d_m), kernel K14.  d_m holds n doubles: usually what
+ * smvp_csr_diagonal / smvp_tjds_diagonal gave (Jacobi), but any positive vector is accepted.  Options, `dot` and the reason codes
+ * are K12's, unchanged: smvp_cg_opts_t, the dot above, SMVP_CG_*.  Every other operation is one correctly rounded IEEE operation per
+ * element (alpha * p_i is rounded, then the sum is rounded); z_i = r_i / m_i is an IEEE double division -- no reciprocal is taken,
+ * no FMA is used.
+ *   bb    = dot(b, b)            thr = (tol * tol) * bb   (tol * tol rounded on the host, the product on the device)
+ *   x_0   = d_x0, or zeros if NULL
+ *   r_0   = b - A x_0            (d_x0 == NULL: r_0 = b bit for bit, no product is run)
+ *   z_0   = r_0 ./ m             p_0 = z_0
+ *   rr_0  = dot(r_0, r_0)        rho_0 = dot(r_0, z_0)
+ *   step 0 rule:   NONFINITE if bb, rr_0 or rho_0 is NaN or +-Inf;  CONVERGED if rr_0 <= thr;  BREAKDOWN if not (rho_0 > 0)
+ *   step k = 1, 2, ...:
+ *     q_k     = A p_{k-1}        the handle's own product, bit for bit: smvp_csr_spmv (current plan), or smvp_tjds_set_x +
+ *                                smvp_tjds_spmv (current mode)
+ *     sigma_k = dot(p_{k-1}, q_k)
+ *     rule A:   NONFINITE if sigma_k is NaN or +-Inf;  BREAKDOWN if not (sigma_k > 0)      -> x stays x_{k-1}, updates = k - 1
+ *     alpha_k = rho_{k-1} / sigma_k
+ *     x_k = x_{k-1} + alpha_k * p_{k-1}        r_k = r_{k-1} - alpha_k * q_k        z_k = r_k ./ m
+ *     rr_k    = dot(r_k, r_k)                  rho_k = dot(r_k, z_k)
+ *     rule B:   NONFINITE if rr_k or rho_k is NaN or +-Inf;  CONVERGED if rr_k <= thr;  BREAKDOWN if not (rho_k > 0);
+ *               MAX_STEPS if k == max_steps                                               -> x = x_k, updates = k
+ *     beta_k  = rho_k / rho_{k-1}              p_k = z_k + beta_k * p_{k-1}
+ * No square root is taken: the histories and the result hold squared norms.
+ * The stop rule looks at the residual's own norm rr, not at rho = r.z: smvp_csr_cg can be swapped for smvp_csr_pcg under the same
+ * tol.  d_m is not validated: a zero or negative element shows up as NONFINITE or BREAKDOWN under the rules above (step 0's
+ * BREAKDOWN is what an M that is visibly not positive definite gets).  With d_m all ones every number is smvp_csr_cg's, bit for bit.
+ * The device evaluates the rules at EVERY step; the first that holds, in the order written, is the `reason`, and from then on
+ * nothing is written to x or to the histories.  The host reads a status block at looked steps only -- step 0, every k with
+ * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, updates, reason, the three histories and every bit
+ * of d_x do not depend on check_every.  Preconditioned BiCGSTAB, other preconditioners and the sharded handles are out of scope. */
+typedef struct smvp_pcg_result {
+    int steps;   /* products of a direction done (the one for r_0 is not counted) */
+    int updates; /* updates of x done: steps, or steps - 1 after rule A */
+    int reason;  /* SMVP_CG_* */
+    int pad;
+    double rr;   /* rr_updates: the squared residual norm that belongs to d_x */
+    double rz;   /* rho_updates = dot(r, z), likewise */
+    double bb;   /* dot(b, b) */
+} smvp_pcg_result_t;
+/*   - d_b, d_m: n doubles each.  d_x0: n doubles, NULL = zeros.  d_x: n doubles; the iterates live in it, and it holds x_updates
+ *     afterwards.  d_x may be the same pointer as d_x0; any other overlap of the two, and any overlap of d_x with d_b or d_m, is
+ *     SMVP_ERR_INVALID.  d_b and d_m are only read.  After SMVP_ERR_HIP the content of d_x is unspecified.
+ *   - rr_each, rz_each: caller-owned HOST arrays of max_steps + 1 doubles, filled 0 .. updates with rr and rho.  sigma_each:
+ *     max_steps doubles, filled 0 .. steps - 1 with sigma_1 .. sigma_steps.  Any of the three may be NULL.  They come from a
+ *     device-side history copied back once at the end, and are left untouched beyond the filled elements.
+ *   - The call returns after the work on `stream` has finished.  It allocates its workspace per call -- three vectors (z is never
+ *     stored: r_i / m_i is divided again where it is needed, the same bits), the partials of three dots, the histories, two status
+ *     blocks -- and frees it on every way out.  Beside the product a step is three launches and twelve passes over a vector (p, q
+ *     read; q, r, m read, r written; x, p, r, m read, x, p written): K12's ten and two reads of m.
+ *   - SMVP_ERR_INVALID for: a NULL handle, opts, result, d_b or d_m (before any HIP call); a struct_size that is not this library's;
+ *     max_steps < 1, check_every < 1, tol negative, NaN or infinite; rows != cols; a NULL d_x with n > 0; the overlaps above; a
+ *     capturing stream.  Nothing is enqueued then, d_x and *result are left untouched, and a capturing stream's capture stays valid.
+ *   - SMVP_ERR_UNSUPPORTED (likewise) for a CSR handle that is not plain CSR, and for a TJDS handle in ATOMIC mode or with
+ *     ref-quirks on, as for the power method.
+ *   - n == 0: SMVP_OK, steps 0, updates 0, reason SMVP_CG_CONVERGED, rr = rz = bb = +0.0.
+ *   - State: as after smvp_csr_cg / smvp_tjds_cg -- a CSR handle's plan is untouched; a TJDS handle's permuted operand is afterwards
+ *     that of the last direction multiplied: call smvp_tjds_set_x again before the next smvp_tjds_spmv. */
+int smvp_csr_pcg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x, const double *d_m,
+                 smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each, void *stream);
+int smvp_tjds_pcg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x, const double *d_m,
+                  smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each, void *stream);
 
 /* ------------------------------------------------- BiCGSTAB */
 /* A x = b for a general (non-symmetric) square A on a handle the caller already holds, kernel K13 (new: the reference only

@@ -184,6 +184,15 @@ int cg_check_args(const char *fn, const void *h, const smvp_cg_opts_t *opts, con
 int cg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
            smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream, const HandleProduct &product);
 
+// ------------------------------------------------------------- conjugate gradients with a diagonal preconditioner (K14)
+// smvp_pcg.hip runs K12's steps with z = r ./ m around the same product hook, checked and handed over as for K12.  pcg_check_args
+// makes no HIP call; pcg_run checks the operands and the stream, then allocates, iterates and frees.
+int pcg_check_args(const char *fn, const void *h, const smvp_cg_opts_t *opts, const smvp_pcg_result_t *result, const double *d_b,
+                   const double *d_m);
+int pcg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+            const double *d_m, smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each, void *stream,
+            const HandleProduct &product);
+
 // ------------------------------------------------------------------------------------------------- BiCGSTAB (K13)
 // smvp_bicgstab.hip runs the steps around the same product hook, two products a step, checked and handed over as for K12.
 int bicgstab_check_args(const char *fn, const void *h, const smvp_bicgstab_opts_t *opts, const smvp_bicgstab_result_t *result,

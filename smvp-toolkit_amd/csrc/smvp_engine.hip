@@ -994,6 +994,35 @@ extern "C" int smvp_csr_cg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const doub
                         [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
 }
 
+// K14 on a CSR handle: the steps are smvp_pcg.hip's, the product is smvp_csr_spmv's on the current plan (which it leaves as it is)
+extern "C" int smvp_csr_pcg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                            const double *d_m, smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each,
+                            void *stream)
+{
+    if (int rc = smvp::pcg_check_args("smvp_csr_pcg", h, opts, result, d_b, d_m))
+        return rc;
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_pcg: plain CSR handles only (this one belongs to a TJDS matrix)");
+    return smvp::pcg_run("smvp_csr_pcg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, d_m, result, rr_each, rz_each, sigma_each,
+                         stream, [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+}
+
+// K14: the diagonal from the handle's own arrays (val is read in place: adopted values changed in place are seen).  No plan, nothing
+// of the handle is written; the group of lanes a row gets follows the mean row length, the VECTOR plan's rule.
+extern "C" int smvp_csr_diagonal(const smvp_csr_t *h, double *d_diag, void *stream)
+{
+    if (!h || (h->rows > 0 && !d_diag))
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_diagonal: null %s", !h ? "handle" : "d_diag");
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_diagonal: plain CSR handles only (this one belongs to a TJDS matrix)");
+    DeviceScope on(h->device);
+    const hipError_t e = smvp::launch_csr_diagonal(pow2_at_least(h->rows > 0 ? (double)h->nnz / h->rows : 0.0), h->d_row_ptr, h->d_col_ind,
+                                                   h->d_val, d_diag, h->rows, h->cols, h->row0, (hipStream_t)stream);
+    if (e != hipSuccess)
+        return smvp::fail(SMVP_ERR_HIP, "smvp_csr_diagonal: launch failed: %s", hipGetErrorString(e));
+    return SMVP_OK;
+}
+
 // K13 on a CSR handle: the steps are smvp_bicgstab.hip's, both products smvp_csr_spmv's on the current plan (which they leave as it is)
 extern "C" int smvp_csr_bicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                                  smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream)

@@ -48,6 +48,12 @@ int build_tjds_spmm_plan(const int *row_ind, const int *start_pos, const int *pe
 hipError_t launch_tjds_spmm(const int *ptr, const int *pos, const int *col, const double *val, const int *order, const double *X,
                             long long ldx, double *Y, long long ldy, int rows, int k, hipStream_t stream);
 void tjds_spmm_kernel_name(int k, char *name, size_t cap);  // the passes' kernel symbols
+// K14 (smvp_diagonal.hip): d[i] = the stored entries (i, i) added in storage order from +0.0.  CSR: a group of lanes_per_row lanes
+// (2 .. 64, a power of two) per row, the diagonal of row r at column first_row + r; TJDS: lane k walks permuted column k
+hipError_t launch_csr_diagonal(int lanes_per_row, const int *row_ptr, const int *col_ind, const double *val, double *d, int rows,
+                               int cols, long long first_row, hipStream_t stream);
+hipError_t launch_tjds_diagonal(const int *start_pos, const int *row_ind, const double *val, const int *perm, double *d, int rows,
+                                int cols, int num_diag, hipStream_t stream);
 // smvp_csr_create_transposed (smvp_convert_device.hip): the entries of a CSR matrix with row and column swapped, storage order
 hipError_t launch_csr_swapped_coo(const int *row_ptr, const int *col_ind, const double *val, int rows, int nnz, smvp_coo_t *coo,
                                   hipStream_t stream);

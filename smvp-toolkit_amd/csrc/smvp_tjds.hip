@@ -419,6 +419,39 @@ extern "C" int smvp_tjds_cg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const do
                         });
 }
 
+// K14 on a TJDS handle: the steps are smvp_pcg.hip's, the product is K11's -- smvp_tjds_set_x + smvp_tjds_spmv in a mode that
+// overwrites y and gives the same bits on every run
+extern "C" int smvp_tjds_pcg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                             const double *d_m, smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each,
+                             void *stream)
+{
+    if (int rc = smvp::pcg_check_args("smvp_tjds_pcg", h, opts, result, d_b, d_m))
+        return rc;
+    if (!overwrites_y(h))
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_pcg: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
+                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
+    return smvp::pcg_run("smvp_tjds_pcg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, d_m, result, rr_each, rz_each, sigma_each,
+                         stream, [h, stream](const double *x, double *y) {
+                             if (int rc = smvp_tjds_set_x(h, x, stream))
+                                 return rc;
+                             return smvp_tjds_spmv(h, y, stream);
+                         });
+}
+
+// K14: the diagonal from the handle's own arrays (the true start_pos, not the ref-quirks edit of the plan; val is read in place).  No
+// plan, no x_perm, nothing of the forward product's state is read or written.
+extern "C" int smvp_tjds_diagonal(const smvp_tjds_t *h, double *d_diag, void *stream)
+{
+    if (!h || (h->rows > 0 && !d_diag))
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_diagonal: null %s", !h ? "handle" : "d_diag");
+    DeviceScope on(h->device);
+    const hipError_t e = smvp::launch_tjds_diagonal(h->d_start_pos, h->d_row_ind, h->d_val, h->d_perm, d_diag, h->rows, h->cols,
+                                                    h->num_diag, (hipStream_t)stream);
+    if (e != hipSuccess)
+        return smvp::fail(SMVP_ERR_HIP, "smvp_tjds_diagonal: launch failed: %s", hipGetErrorString(e));
+    return SMVP_OK;
+}
+
 // K13 on a TJDS handle: the steps are smvp_bicgstab.hip's, both products K11's -- smvp_tjds_set_x + smvp_tjds_spmv in a mode that
 // overwrites y and gives the same bits on every run
 extern "C" int smvp_tjds_bicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,

@@ -104,6 +104,11 @@ class CgResult(C.Structure):
     _fields_ = [("steps", C.c_int), ("updates", C.c_int), ("reason", C.c_int), ("pad", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
 
 
+class PcgResult(C.Structure):
+    _fields_ = [("steps", C.c_int), ("updates", C.c_int), ("reason", C.c_int), ("pad", C.c_int), ("rr", C.c_double), ("rz", C.c_double),
+                ("bb", C.c_double)]
+
+
 class BicgstabOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("max_steps", C.c_int), ("check_every", C.c_int), ("tol", C.c_double)]
 
@@ -150,6 +155,7 @@ EXPORTS = [
     "smvp_tjds_spmm_transposed", "smvp_tjds_spmm_transposed_describe", "smvp_tjds_spmm", "smvp_tjds_spmm_describe",
     "smvp_power_opts_default", "smvp_csr_power_method", "smvp_tjds_power_method",
     "smvp_vector_dot", "smvp_cg_opts_default", "smvp_csr_cg", "smvp_tjds_cg",
+    "smvp_csr_diagonal", "smvp_tjds_diagonal", "smvp_csr_pcg", "smvp_tjds_pcg",
     "smvp_bicgstab_opts_default", "smvp_csr_bicgstab", "smvp_tjds_bicgstab",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
@@ -207,6 +213,10 @@ def lib():
         L.smvp_cg_opts_default.restype = None
         L.smvp_csr_cg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, C.POINTER(CgResult), vp, vp, vp]
         L.smvp_tjds_cg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, C.POINTER(CgResult), vp, vp, vp]
+        L.smvp_csr_diagonal.argtypes = [vp, vp, vp]
+        L.smvp_tjds_diagonal.argtypes = [vp, vp, vp]
+        L.smvp_csr_pcg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
+        L.smvp_tjds_pcg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
         L.smvp_bicgstab_opts_default.argtypes = [C.POINTER(BicgstabOpts)]
         L.smvp_bicgstab_opts_default.restype = None
         L.smvp_csr_bicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
@@ -597,6 +607,26 @@ def _cg(fn, handle, b, x, x0, max_steps, tol, check_every, stream):
     return r, rr[:r.updates + 1], sigma[:r.steps]
 
 
+def _diagonal(fn, handle, rows, out, stream):
+    """smvp_csr_diagonal / smvp_tjds_diagonal into `out`, a contiguous float64 CUDA tensor of `rows` elements."""
+    _device_vectors(out=out)
+    if str(out.dtype) != "torch.float64" or out.numel() != rows or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float64 tensor of %d elements (it has %d of %s)" % (rows, out.numel(), out.dtype))
+    _check(getattr(lib(), fn)(handle, _dev_ptr(out), _stream_ptr(stream)), fn)
+    return out
+
+
+def _pcg(fn, handle, b, x, m, x0, max_steps, tol, check_every, stream):
+    """smvp_csr_pcg / smvp_tjds_pcg -> (PcgResult, rr_each, rz_each, sigma_each), the histories cut to the filled elements."""
+    _device_vectors(b=b, x=x, m=m, x0=x0)
+    o = cg_opts(max_steps, tol, check_every)
+    r = PcgResult()
+    rr, rz, sigma = np.zeros(max(int(max_steps), 0) + 1), np.zeros(max(int(max_steps), 0) + 1), np.zeros(max(int(max_steps), 1))
+    _check(getattr(lib(), fn)(handle, C.byref(o), _dev_ptr(b), _dev_ptr(x0), _dev_ptr(x), _dev_ptr(m), C.byref(r), _p(rr), _p(rz),
+                              _p(sigma), _stream_ptr(stream)), fn)
+    return r, rr[:r.updates + 1], rz[:r.updates + 1], sigma[:r.steps]
+
+
 def bicgstab_opts(max_steps=100, tol=1e-10, check_every=10):
     """smvp_bicgstab_opts_t from smvp_bicgstab_opts_default with the three fields set."""
     o = BicgstabOpts()
@@ -697,6 +727,19 @@ class CsrMatrix:
         sigma_each result.steps values of p.Ap.  Nothing depends on check_every but how often the host waits."""
         return _cg("smvp_csr_cg", self._h, b, x, x0, max_steps, tol, check_every, stream)
 
+    def diagonal(self, out, stream=None):
+        """The diagonal of the matrix into `out`, a float64 CUDA tensor of `rows` elements (smvp_csr_diagonal, K14): element i is
+        the sum of the stored entries (i, i) in storage order from +0.0 -- on a row block, of the entries at column first_row + i.
+        Asynchronous on `stream`; needs no plan and leaves the handle alone.  Returns `out`."""
+        return _diagonal("smvp_csr_diagonal", self._h, self.rows, out, stream)
+
+    def pcg(self, b, x, m, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Conjugate gradients for A x = b preconditioned with diag(m) (smvp_csr_pcg, K14; A symmetric positive definite, m
+        positive -- usually diagonal()'s output): operands as cg(), m a float64 CUDA tensor of `rows` elements.  Returns
+        (PcgResult, rr_each, rz_each, sigma_each) after the work on `stream` has finished: rr_each and rz_each have
+        result.updates + 1 values of r.r and r.z, sigma_each result.steps values of p.Ap.  The stop rule is cg()'s, on r.r."""
+        return _pcg("smvp_csr_pcg", self._h, b, x, m, x0, max_steps, tol, check_every, stream)
+
     def bicgstab(self, b, x, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
         """BiCGSTAB for A x = b on this handle's product (smvp_csr_bicgstab, K13; A any square matrix): b, x and x0 (None = zeros)
         are float64 CUDA tensors of `rows` elements, x receives the solution and may be x0.  Returns (BicgstabResult, rr_each,
@@ -791,6 +834,18 @@ class TjdsMatrix:
         TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.cg.  Afterwards the handle's permuted operand is the last
         direction's: call set_x again before the next spmv."""
         return _cg("smvp_tjds_cg", self._h, b, x, x0, max_steps, tol, check_every, stream)
+
+    def diagonal(self, out, stream=None):
+        """The diagonal of the matrix into `out`, a float64 CUDA tensor of `rows` elements (smvp_tjds_diagonal, K14), from the TJDS
+        arrays themselves: the bits CsrMatrix.diagonal gives for the same entries.  Asynchronous on `stream`; needs no set_x and
+        leaves the forward product's state alone.  Returns `out`."""
+        return _diagonal("smvp_tjds_diagonal", self._h, self.rows, out, stream)
+
+    def pcg(self, b, x, m, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Conjugate gradients preconditioned with diag(m) on this handle's product in its current mode (smvp_tjds_pcg, K14;
+        ROW_GATHER or TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.pcg.  Afterwards the handle's permuted operand is
+        the last direction's: call set_x again before the next spmv."""
+        return _pcg("smvp_tjds_pcg", self._h, b, x, m, x0, max_steps, tol, check_every, stream)
 
     def bicgstab(self, b, x, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
         """BiCGSTAB for A x = b on this handle's product in its current mode (smvp_tjds_bicgstab, K13; ROW_GATHER or TWO_PHASE, no
