@@ -69,6 +69,8 @@ const char *smvp_version_string(void); /* "0.6.4" */
  *                            the results are the same bits either way
  *   "tjds_index" 0 | 1 | 2: 16-bit position words (default) / 32-bit sorted / 32-bit columns
  *   "sharded_threads" 1: the sharded layer's issuing threads with one GPU too     "mm_threads" n: the reader's threads (1 = serial)
+ *   "trsv_chain_width" 256 | 512 | 1024: the widest level a triangular solve's chain takes (default 256), read by smvp_csr_trsv_create
+ *   "trsv_lanes_by_mean" 1: a wide level's lanes per row from the triangle's mean row length alone (default: mean and longest row)
  * Unknown names are SMVP_ERR_INVALID. */
 int smvp_set_option(const char *name, int value);
 int smvp_get_option(const char *name, int *value); /* -1 = not set */
@@ -696,7 +698,8 @@ int smvp_tjds_diagonal(const smvp_tjds_t *h, double *d_diag, void *stream);
  * The device evaluates the rules at EVERY step; the first that holds, in the order written, is the `reason`, and from then on
  * nothing is written to x or to the histories.  The host reads a status block at looked steps only -- step 0, every k with
  * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, updates, reason, the three histories and every bit
- * of d_x do not depend on check_every.  Preconditioned BiCGSTAB, other preconditioners and the sharded handles are out of scope. */
+ * of d_x do not depend on check_every.  Preconditioned BiCGSTAB, a preconditioner other than a diagonal inside this solver (the
+ * triangular solves others apply are K15, below) and the sharded handles are out of scope. */
 typedef struct smvp_pcg_result {
     int steps;   /* products of a direction done (the one for r_0 is not counted) */
     int updates; /* updates of x done: steps, or steps - 1 after rule A */
@@ -728,6 +731,78 @@ int smvp_csr_pcg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, c
                  smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each, void *stream);
 int smvp_tjds_pcg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x, const double *d_m,
                   smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each, void *stream);
+
+/* ------------------------------------------------- sparse triangular solves */
+/* T x = b where T is a triangle of a square plain-CSR handle's matrix AS STORED, kernel K15 (new: the reference only multiplies).
+ * The operation under a Gauss-Seidel or SOR sweep, symmetric Gauss-Seidel / SSOR preconditioning and the application of an
+ * incomplete factorisation the caller brings.  Entries of the other triangle are skipped, not refused: a sweep on a full A needs
+ * no extracted copy.  Rows are taken in ascending order (LOWER) or descending order (UPPER):
+ *   s_i = +0.0;  d_i = +0.0
+ *   for every stored entry p of row i in ascending storage position (columns need not be sorted, repeats allowed):
+ *     c = col_ind[p]
+ *     c == i                          : d_i = d_i + val[p]            (smvp_csr_diagonal's rule; skipped, val not read, for DIAG_UNIT)
+ *     c <  i (LOWER) / c > i (UPPER)  : s_i = s_i + val[p] * x[c]     (the product rounded, then the sum rounded: no FMA, as everywhere)
+ *     otherwise                       : skipped
+ *   x_i = (b_i - s_i) / d_i     (DIAG_STORED: one IEEE subtraction, one IEEE division, no reciprocal)
+ *   x_i =  b_i - s_i            (DIAG_UNIT)
+ * d_i is not validated: a missing or zero diagonal gives +-Inf or NaN by the rules above, as d_m does in smvp_csr_pcg.  How a row's
+ * entries are loaded is the library's business (a lane per row, or a group of lanes); the order of the additions is the one written,
+ * so every element of x has one right answer, the serial substitution loop's, the same on every run.
+ *
+ * Levels.  level(i) = 0 if row i has no stored off-diagonal entry inside the triangle, else 1 + the largest level(c) over those
+ * entries.  Levels are structural: an explicitly stored 0.0 counts.  The schedule's `order` lists the rows by (level, row index)
+ * ascending, for both uplo; level_ptr (levels + 1 elements) delimits the levels in it.  Rows of one level do not depend on each
+ * other.  A level of more than chain_width rows is one launch over its rows; a maximal run of consecutive levels of at most
+ * chain_width rows each (a chain) is one launch of one workgroup with a workgroup barrier between its levels, so
+ * launches = wide levels + chains.  No kernel waits on a value another workgroup writes in the same launch -- no flags, no grid
+ * barrier, no atomics: the order between workgroups comes from the kernel boundaries on the stream alone.
+ *
+ * Out of scope: TJDS handles (the format stores by columns: it needs a column-oriented solve), sharded handles, a block of k
+ * right-hand sides, the transposed solve T^T x = b (for a symmetric matrix stored in full the other uplo serves), an analysis on
+ * the device, and a solver that uses the triangles as a preconditioner: this call is the building block, a Gauss-Seidel / SSOR
+ * preconditioned solver on it the follow-up. */
+enum { SMVP_TRSV_LOWER = 0, SMVP_TRSV_UPPER = 1 };
+enum { SMVP_TRSV_DIAG_STORED = 0, SMVP_TRSV_DIAG_UNIT = 1 };
+typedef struct smvp_trsv smvp_trsv_t; /* a plan: borrows the handle's arrays, owns level_ptr / order on the device */
+typedef struct smvp_trsv_info {
+    unsigned struct_size;  /* set by the caller to sizeof(smvp_trsv_info_t) before the call; another size is SMVP_ERR_INVALID */
+    int levels;
+    int max_level_width;   /* rows of the widest level */
+    int launches;          /* kernels one solve enqueues: wide levels + chains */
+    int chains;
+    int chain_width;       /* a level of at most so many rows joins a chain: the library's constant, 256, unless the plan option
+                              "trsv_chain_width" said otherwise when the plan was made */
+    int missing_diagonals; /* rows with no stored (i, i): reported for both diag settings */
+    int lanes_per_row;     /* lanes a row of a wide level gets (from the triangle's mean and longest row) */
+    long long entries;     /* stored entries one solve reads: the triangle's off-diagonals, plus the diagonal matches for DIAG_STORED */
+    double plan_bytes;     /* device memory the plan owns: level_ptr and order */
+    double build_ms;       /* host wall time of smvp_csr_trsv_create: copies back, analysis, counting sort, upload */
+} smvp_trsv_info_t;
+/*   - smvp_csr_trsv_create: the level recurrence is sequential, so the analysis runs on the HOST in one O(nnz) pass: row_ptr is the
+ *     handle's host copy, col_ind comes back from the device once (the handle keeps no host copy of it, adopted or uploaded); then a
+ *     counting sort by level and one upload of level_ptr and order.  build_ms reports the cost.  The call waits for `stream`,
+ *     allocates, and refuses a capturing stream.  The plan holds pointers into the handle's row_ptr / col_ind / val and copies no
+ *     matrix data: the handle must outlive it.  `val` changed in place is seen by the next solve; a changed STRUCTURE needs a new
+ *     plan.  Any number of plans per handle (lower and upper together is the normal case).  The handle's own state and plans are
+ *     untouched: a product afterwards gives the bits it gave before.
+ *   - smvp_trsv_solve: d_b and d_x are n doubles on the handle's device.  Asynchronous on `stream`; allocates nothing, synchronises
+ *     nothing and can be captured from the first call on: the graph is a plain chain of kernels with no parallel branches.  d_x ==
+ *     d_b (exactly the same pointer) is allowed -- row i reads b_i before it writes x_i; any other overlap is SMVP_ERR_INVALID.
+ *     Every one of the n doubles of d_x is written, and nothing else.  A plan is used by one stream at a time.
+ *   - smvp_trsv_schedule: level_ptr (levels + 1 ints) and order (n ints) into caller-owned HOST arrays; either may be NULL.
+ *   - SMVP_ERR_INVALID (nothing enqueued, outputs untouched, smvp_last_error names the argument): a NULL out, h, t, or a NULL d_b /
+ *     d_x with n > 0; uplo / diag out of range; rows != cols; the partial overlap above; a capturing stream at create.
+ *     SMVP_ERR_UNSUPPORTED: a handle that is not plain CSR (as for smvp_csr_diagonal), and a row block (first_row != 0).
+ *   - n == 0: everything succeeds with levels 0, launches 0.
+ *   - smvp_csr_trsv_levels is the analysis itself on HOST arrays, no device touched: level_of_row (rows ints) and *levels.
+ *     SMVP_ERR_INVALID for uplo out of range, rows < 0, a NULL row_ptr / level_of_row with rows > 0, a NULL col_ind with entries, a
+ *     NULL levels, a row_ptr that is not a non-decreasing sequence from 0, a column outside [0, rows); the outputs are untouched. */
+int smvp_csr_trsv_create(smvp_trsv_t **out, const smvp_csr_t *h, int uplo, int diag, void *stream);
+int smvp_trsv_solve(smvp_trsv_t *t, const double *d_b, double *d_x, void *stream);
+int smvp_trsv_info(const smvp_trsv_t *t, smvp_trsv_info_t *out);
+int smvp_trsv_schedule(const smvp_trsv_t *t, int *level_ptr, int *order);
+void smvp_trsv_destroy(smvp_trsv_t *t);
+int smvp_csr_trsv_levels(int rows, const int *row_ptr, const int *col_ind, int uplo, int *level_of_row, int *levels);
 
 /* ------------------------------------------------- BiCGSTAB */
 /* A x = b for a general (non-symmetric) square A on a handle the caller already holds, kernel K13 (new: the reference only

@@ -1,7 +1,7 @@
 // host_san_driver.cpp -- exercises the host side of libsmvp_amd under sanitizers (make -C smvp-toolkit_amd host-san).
 //
-// Not part of the product: a test driver linked against the seven host translation units only (reader, converters,
-// report writer, cache, CISR export, synthetic generators, error text -- no HIP), built with
+// Not part of the product: a test driver linked against the eight host translation units only (reader, converters,
+// report writer, cache, CISR export, synthetic generators, the triangular solves' analysis, error text -- no HIP), built with
 // g++ -fsanitize=address,undefined and, for the parallel Matrix Market tokeniser, -fsanitize=thread (SURVEY 5,
 // "race detection / sanitizers": the reference has none, CMakeLists.txt:33-34 even comments -Wall out).
 // tests/test_host_sanitizers.py runs it over the reference's sample files, malformed inputs, crafted cache files.
@@ -207,6 +207,44 @@ static int run_synth(const std::string &tmp)
     char outp[64];
     rc = smvp_generate_report_text("x.mtx", (tmp + "/no/such/dir").c_str(), "CSR", 0, 0, 1, nullptr, &st, 1ul, outp, sizeof outp);
     printf("report into a missing directory: rc %d\n", rc);
+    // ---- K15's host analysis (smvp_trsv_plan.cpp): empty, one row, a chain, unsorted columns with repeats, arrays it must refuse
+    int levels = -1;
+    MUST(smvp_csr_trsv_levels(0, rp1.data(), nullptr, SMVP_TRSV_LOWER, nullptr, &levels));
+    MUST(smvp_csr_trsv_levels(0, nullptr, nullptr, SMVP_TRSV_UPPER, nullptr, &levels));
+    std::vector<int> lone{0, 2}, lone_c{0, 0}, lv(8, -1);
+    MUST(smvp_csr_trsv_levels(1, lone.data(), lone_c.data(), SMVP_TRSV_UPPER, lv.data(), &levels));
+    if (levels != 1 || lv[0] != 0)
+        ++g_bad, fprintf(stderr, "FAILED: one row has %d levels, level %d\n", levels, lv[0]);
+    const int n = 5000;
+    std::vector<int> chain_rp((size_t)n + 1), chain_c, chain_lv((size_t)n);
+    for (int i = 0; i < n; ++i) {  // (i, i) and (i, i - 1): n levels for LOWER, one for UPPER
+        chain_rp[(size_t)i] = (int)chain_c.size();
+        chain_c.push_back(i);
+        if (i)
+            chain_c.push_back(i - 1);
+    }
+    chain_rp[(size_t)n] = (int)chain_c.size();
+    MUST(smvp_csr_trsv_levels(n, chain_rp.data(), chain_c.data(), SMVP_TRSV_LOWER, chain_lv.data(), &levels));
+    if (levels != n || chain_lv[(size_t)n - 1] != n - 1)
+        ++g_bad, fprintf(stderr, "FAILED: the chain has %d levels\n", levels);
+    MUST(smvp_csr_trsv_levels(n, chain_rp.data(), chain_c.data(), SMVP_TRSV_UPPER, chain_lv.data(), &levels));
+    if (levels != 1)
+        ++g_bad, fprintf(stderr, "FAILED: the chain's upper triangle has %d levels\n", levels);
+    std::vector<int> mix_rp{0, 2, 5, 9, 9}, mix_c{3, 0, 1, 0, 0, 2, 1, 1, 0};  // unsorted, repeated, an empty last row
+    for (int uplo : {SMVP_TRSV_LOWER, SMVP_TRSV_UPPER})
+        MUST(smvp_csr_trsv_levels(4, mix_rp.data(), mix_c.data(), uplo, lv.data(), &levels));
+    if (levels != 2 || lv[0] != 1 || lv[3] != 0)
+        ++g_bad, fprintf(stderr, "FAILED: the mixed case's upper triangle: %d levels, row 0 at %d\n", levels, lv[0]);
+    mix_c[4] = 4;  // a column past the last row, a decreasing row_ptr, a bad uplo, null arrays: refused before anything is read or written
+    rc = smvp_csr_trsv_levels(4, mix_rp.data(), mix_c.data(), SMVP_TRSV_UPPER, lv.data(), &levels);
+    mix_c[4] = 0, mix_rp[2] = 1;
+    rc += smvp_csr_trsv_levels(4, mix_rp.data(), mix_c.data(), SMVP_TRSV_LOWER, lv.data(), &levels);
+    rc += smvp_csr_trsv_levels(4, mix_rp.data(), mix_c.data(), 2, lv.data(), &levels);
+    rc += smvp_csr_trsv_levels(4, nullptr, mix_c.data(), SMVP_TRSV_LOWER, lv.data(), &levels);
+    rc += smvp_csr_trsv_levels(4, mix_rp.data(), mix_c.data(), SMVP_TRSV_LOWER, nullptr, nullptr);
+    printf("five refused trsv analyses: rc sum %d\n", rc);
+    if (rc != 5 * SMVP_ERR_INVALID)
+        ++g_bad;
     printf("version %s\n", smvp_version_string());
     return 0;
 }

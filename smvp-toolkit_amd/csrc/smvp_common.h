@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <vector>
 
 namespace smvp {
 // The most entries a matrix may have (smvp_csr_create, smvp_tjds_create and the device-side converters): 32-bit indices like
@@ -14,6 +15,21 @@ constexpr long long kMaxEntries = 2147483647ll - 65536;
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void clear_error();
 int option(const char *name, int fallback);  // smvp_set_option's value, or `fallback` where it is not set (smvp_error.cpp)
+
+// K15, the host analysis of a triangular solve (smvp_trsv_plan.cpp): the levels of the `uplo` triangle's rows, the rows listed by
+// (level, row) ascending, and what the triangle holds; then the launches of a schedule -- [first, last) levels each, a chain (one
+// workgroup, a barrier between its levels) or one wide level
+struct TrsvSchedule {
+    std::vector<int> level_of_row, level_ptr, order;
+    int levels = 0, max_level_width = 0, missing_diagonals = 0, max_row_entries = 0;  // (the longest row of the triangle, its diagonal included)
+    long long off_entries = 0, diag_entries = 0;  // stored entries strictly inside the triangle / on the diagonal
+};
+struct TrsvLaunch {
+    int first, last;
+    bool chain;
+};
+int trsv_analyse(int rows, const int *row_ptr, const int *col_ind, int uplo, TrsvSchedule *out);
+void trsv_launches(const std::vector<int> &level_ptr, int chain_width, std::vector<TrsvLaunch> *out, int *chains);
 }  // namespace smvp
 
 // internal, device side (smvp_convert_device.hip): see its definition

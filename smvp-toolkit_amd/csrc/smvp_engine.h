@@ -153,6 +153,17 @@ std::string csr_owner_kernel_name(const smvp_csr_t *h);
 // bytes of device memory the current launch plan keeps beside row_ptr / col_ind / val
 double csr_plan_bytes(const smvp_csr_t *h);
 
+// what a plan beside the handle (K15, smvp_trsv.hip) borrows of a CSR handle: its device arrays, the host copy of row_ptr (valid as
+// long as the handle lives) and where it stands
+struct CsrView {
+    int device, rows, cols, nnz, flavor;
+    long long first_row;
+    const int *d_row_ptr, *d_col_ind;
+    const double *d_val;
+    const int *h_row_ptr;
+};
+CsrView csr_view(const smvp_csr_t *h);
+
 // ---------------------------------------------------------------------------------------------------- the timed run
 // Per format: the {first, last} tick pairs one stamped product writes (0: the current plan cannot time itself on the device -- see
 // StampTimer), the grid of the repeating launch (0: no such form), `reps` products in one launch of it, and one product whose

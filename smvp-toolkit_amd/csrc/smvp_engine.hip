@@ -1023,6 +1023,12 @@ extern "C" int smvp_csr_diagonal(const smvp_csr_t *h, double *d_diag, void *stre
     return SMVP_OK;
 }
 
+// K15 (smvp_trsv.hip) plans beside the handle: what it borrows
+smvp::CsrView smvp::csr_view(const smvp_csr_t *h)
+{
+    return {h->device, h->rows, h->cols, h->nnz, h->flavor, h->row0, h->d_row_ptr, h->d_col_ind, h->d_val, h->h_row_ptr.data()};
+}
+
 // K13 on a CSR handle: the steps are smvp_bicgstab.hip's, both products smvp_csr_spmv's on the current plan (which they leave as it is)
 extern "C" int smvp_csr_bicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                                  smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream)

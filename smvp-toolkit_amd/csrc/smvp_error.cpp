@@ -42,6 +42,8 @@ Option g_options[] = {
     {"binned_overlap", {-1}},   // 0: pass A behind the near part on one stream (default 1: beside it on a stream of its own)
     {"tjds_index", {-1}},       // the one-kernel TJDS product's index stream: 0 = 16-bit position words (default), 1 = 32-bit sorted, 2 = 32-bit columns
     {"sharded_threads", {-1}},  // 1: smvp_sharded_* uses its issuing threads with ONE GPU too (default 0: the caller's thread)
+    {"trsv_chain_width", {-1}}, // rows of the widest level a triangular solve's chain takes: 256 (default), 512 or 1024 -- a lane of its workgroup takes 1, 2 or 4
+    {"trsv_lanes_by_mean", {-1}}, // 1: a wide level's lanes per row from the triangle's mean row length alone (default 0: from the geometric mean of mean and longest)
     {"mm_threads", {-1}},       // threads of the Matrix Market tokeniser (default: up to 16 for files of 8 MB and more; 1 = serial; n > 1 forces the parallel path)
 };
 Option *find_option(const char *name)

@@ -117,7 +117,15 @@ class BicgstabResult(C.Structure):
     _fields_ = [("steps", C.c_int), ("full", C.c_int), ("half", C.c_int), ("reason", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
 
 
+class TrsvInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("levels", C.c_int), ("max_level_width", C.c_int), ("launches", C.c_int), ("chains", C.c_int),
+                ("chain_width", C.c_int), ("missing_diagonals", C.c_int), ("lanes_per_row", C.c_int), ("entries", C.c_longlong),
+                ("plan_bytes", C.c_double), ("build_ms", C.c_double)]
+
+
 POWER_CONVERGED, POWER_MAX_STEPS, POWER_ZERO, POWER_NONFINITE = 0, 1, 2, 3
+TRSV_LOWER, TRSV_UPPER = 0, 1
+TRSV_DIAG_STORED, TRSV_DIAG_UNIT = 0, 1
 CG_CONVERGED, CG_MAX_STEPS, CG_BREAKDOWN, CG_NONFINITE = 0, 1, 2, 3
 BICGSTAB_CONVERGED, BICGSTAB_MAX_STEPS, BICGSTAB_BREAKDOWN, BICGSTAB_NONFINITE = 0, 1, 2, 3
 GATHER_NONE, GATHER_OVERLAPPED, GATHER_AFTER = 0, 1, 2
@@ -157,6 +165,7 @@ EXPORTS = [
     "smvp_vector_dot", "smvp_cg_opts_default", "smvp_csr_cg", "smvp_tjds_cg",
     "smvp_csr_diagonal", "smvp_tjds_diagonal", "smvp_csr_pcg", "smvp_tjds_pcg",
     "smvp_bicgstab_opts_default", "smvp_csr_bicgstab", "smvp_tjds_bicgstab",
+    "smvp_csr_trsv_create", "smvp_trsv_solve", "smvp_trsv_info", "smvp_trsv_schedule", "smvp_trsv_destroy", "smvp_csr_trsv_levels",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -221,6 +230,13 @@ def lib():
         L.smvp_bicgstab_opts_default.restype = None
         L.smvp_csr_bicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
         L.smvp_tjds_bicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
+        L.smvp_csr_trsv_create.argtypes = [C.POINTER(vp), vp, ci, ci, vp]
+        L.smvp_trsv_solve.argtypes = [vp, vp, vp, vp]
+        L.smvp_trsv_info.argtypes = [vp, C.POINTER(TrsvInfo)]
+        L.smvp_trsv_schedule.argtypes = [vp, vp, vp]
+        L.smvp_trsv_destroy.argtypes = [vp]
+        L.smvp_trsv_destroy.restype = None
+        L.smvp_csr_trsv_levels.argtypes = [ci, vp, vp, ci, vp, C.POINTER(ci)]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -651,6 +667,61 @@ def _bicgstab(fn, handle, b, x, x0, max_steps, tol, check_every, stream):
     return r, rr[:r.full + 1], ss[:filled]
 
 
+def trsv_levels(rows, row_ptr, col_ind, uplo):
+    """(level_of_row, levels) of the `uplo` triangle of CSR arrays on the host (smvp_csr_trsv_levels, K15): the analysis a
+    TrsvPlan rests on, with no device touched."""
+    rp, ci = _arr(row_ptr, np.int32), _arr(col_ind, np.int32)
+    level = np.zeros(max(int(rows), 1), dtype=np.int32)
+    levels = C.c_int()
+    _check(lib().smvp_csr_trsv_levels(int(rows), _p(rp), _p(ci), int(uplo), _p(level), C.byref(levels)), "smvp_csr_trsv_levels")
+    return level[:max(int(rows), 0)], levels.value
+
+
+class TrsvPlan:
+    """A triangular solve on a CsrMatrix (smvp_trsv_t, K15): T x = b for the `uplo` triangle of the matrix as stored.  It borrows
+    the matrix's device arrays and keeps a reference to the CsrMatrix."""
+
+    def __init__(self, matrix, uplo, diag=TRSV_DIAG_STORED, stream=None):
+        self._t = C.c_void_p()
+        self.matrix, self.rows, self.uplo, self.diag = matrix, matrix.rows, int(uplo), int(diag)
+        _check(lib().smvp_csr_trsv_create(C.byref(self._t), matrix._h, int(uplo), int(diag), _stream_ptr(stream)), "smvp_csr_trsv_create")
+
+    def solve(self, b, x, stream=None):
+        """x = T^-1 b, asynchronous on `stream`: b and x are contiguous float64 CUDA tensors of `rows` elements; x may be b
+        itself.  Returns x."""
+        _device_vectors(b=b, x=x)
+        for name, t in (("b", b), ("x", x)):
+            if str(t.dtype) != "torch.float64" or t.numel() != self.rows or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float64 tensor of %d elements (it has %d of %s)"
+                                 % (name, self.rows, t.numel(), t.dtype))
+        _check(lib().smvp_trsv_solve(self._t, _dev_ptr(b), _dev_ptr(x), _stream_ptr(stream)), "smvp_trsv_solve")
+        return x
+
+    def info(self):
+        """smvp_trsv_info_t as a dict."""
+        i = TrsvInfo()
+        i.struct_size = C.sizeof(TrsvInfo)
+        _check(lib().smvp_trsv_info(self._t, C.byref(i)), "smvp_trsv_info")
+        return {name: getattr(i, name) for name, _ in TrsvInfo._fields_[1:]}
+
+    def schedule(self):
+        """(level_ptr, order): the rows by (level, row) ascending and where each level begins in them."""
+        level_ptr, order = np.zeros(self.info()["levels"] + 1, dtype=np.int32), np.zeros(max(self.rows, 1), dtype=np.int32)
+        _check(lib().smvp_trsv_schedule(self._t, _p(level_ptr), _p(order)), "smvp_trsv_schedule")
+        return level_ptr, order[:self.rows]
+
+    def close(self):
+        if self._t:
+            lib().smvp_trsv_destroy(self._t)
+            self._t = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CsrMatrix:
     """Device-resident CSR matrix (smvp_csr_t).  Arrays may be numpy (copied to HBM) or torch CUDA tensors (adopted)."""
 
@@ -739,6 +810,11 @@ class CsrMatrix:
         (PcgResult, rr_each, rz_each, sigma_each) after the work on `stream` has finished: rr_each and rz_each have
         result.updates + 1 values of r.r and r.z, sigma_each result.steps values of p.Ap.  The stop rule is cg()'s, on r.r."""
         return _pcg("smvp_csr_pcg", self._h, b, x, m, x0, max_steps, tol, check_every, stream)
+
+    def trsv_plan(self, uplo, diag=TRSV_DIAG_STORED, stream=None):
+        """A TrsvPlan for the `uplo` triangle of this matrix as stored (smvp_csr_trsv_create, K15): TRSV_LOWER or TRSV_UPPER,
+        the diagonal as stored or taken as ones.  Analysed on the host once; close the plan before the matrix."""
+        return TrsvPlan(self, uplo, diag, stream)
 
     def bicgstab(self, b, x, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
         """BiCGSTAB for A x = b on this handle's product (smvp_csr_bicgstab, K13; A any square matrix): b, x and x0 (None = zeros)
