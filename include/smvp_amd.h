@@ -698,8 +698,9 @@ int smvp_tjds_diagonal(const smvp_tjds_t *h, double *d_diag, void *stream);
  * The device evaluates the rules at EVERY step; the first that holds, in the order written, is the `reason`, and from then on
  * nothing is written to x or to the histories.  The host reads a status block at looked steps only -- step 0, every k with
  * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, updates, reason, the three histories and every bit
- * of d_x do not depend on check_every.  Preconditioned BiCGSTAB, a preconditioner other than a diagonal inside this solver (the
- * triangular solves others apply are K15, below) and the sharded handles are out of scope. */
+ * of d_x do not depend on check_every.  A preconditioner made of two triangular solves (symmetric Gauss-Seidel, an incomplete
+ * factorisation the caller brings) is smvp_csr_pcg_tri, K16, below.  Preconditioned BiCGSTAB and the sharded handles are out of
+ * scope. */
 typedef struct smvp_pcg_result {
     int steps;   /* products of a direction done (the one for r_0 is not counted) */
     int updates; /* updates of x done: steps, or steps - 1 after rule A */
@@ -758,9 +759,8 @@ int smvp_tjds_pcg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b,
  * barrier, no atomics: the order between workgroups comes from the kernel boundaries on the stream alone.
  *
  * Out of scope: TJDS handles (the format stores by columns: it needs a column-oriented solve), sharded handles, a block of k
- * right-hand sides, the transposed solve T^T x = b (for a symmetric matrix stored in full the other uplo serves), an analysis on
- * the device, and a solver that uses the triangles as a preconditioner: this call is the building block, a Gauss-Seidel / SSOR
- * preconditioned solver on it the follow-up. */
+ * right-hand sides, the transposed solve T^T x = b (for a symmetric matrix stored in full the other uplo serves) and an analysis
+ * on the device.  The solver that uses two plans as a preconditioner is smvp_csr_pcg_tri / smvp_tjds_pcg_tri, K16, below. */
 enum { SMVP_TRSV_LOWER = 0, SMVP_TRSV_UPPER = 1 };
 enum { SMVP_TRSV_DIAG_STORED = 0, SMVP_TRSV_DIAG_UNIT = 1 };
 typedef struct smvp_trsv smvp_trsv_t; /* a plan: borrows the handle's arrays, owns level_ptr / order on the device */
@@ -803,6 +803,52 @@ int smvp_trsv_info(const smvp_trsv_t *t, smvp_trsv_info_t *out);
 int smvp_trsv_schedule(const smvp_trsv_t *t, int *level_ptr, int *order);
 void smvp_trsv_destroy(smvp_trsv_t *t);
 int smvp_csr_trsv_levels(int rows, const int *row_ptr, const int *col_ind, int uplo, int *level_of_row, int *levels);
+
+/* ------------------------------------------------- conjugate gradients preconditioned by two triangular solves */
+/* Conjugate gradients on a square n x n handle's own product, preconditioned with M = T1 diag(m)^-1 T2, kernel K16 (new: the
+ * reference only multiplies).  `first` and `second` are plans of smvp_csr_trsv_create; z = M^-1 r is
+ *   w   = T1^-1 r      smvp_trsv_solve(first, r, z): K15's bits
+ *   v_i = m_i * w_i    one rounded multiplication; skipped entirely when d_m == NULL
+ *   z   = T2^-1 v      smvp_trsv_solve(second, z, z): in place
+ * The plans are the caller's and may belong to ANY plain-CSR handle of n rows on the handle's device; the product may be a CSR or a
+ * TJDS handle's.
+ *   - Symmetric Gauss-Seidel on A itself: first = LOWER / DIAG_STORED on A, d_m = smvp_csr_diagonal of A, second = UPPER /
+ *     DIAG_STORED on A: M = (D + L) D^-1 (D + U).  The solves skip the other triangle: no extracted copy is needed.
+ *   - An incomplete factorisation A ~ F F^T the caller brings: first = LOWER / DIAG_STORED on a handle of F, second = UPPER /
+ *     DIAG_STORED on smvp_csr_create_transposed of it, d_m = NULL.
+ *   - SSOR with omega != 1 needs a handle whose diagonal is scaled by 1 / omega (and d_m to match): building it is the caller's
+ *     business.
+ * Everything else is smvp_csr_pcg's word for word with z = M^-1 r in place of r ./ m: smvp_cg_opts_t, SMVP_CG_*, smvp_pcg_result_t
+ * (rr, rz, bb), the dot above, step 0 and its rule, rule A, rule B in its order (NONFINITE if rr_k or rho_k is NaN or +-Inf;
+ * CONVERGED if rr_k <= thr; BREAKDOWN if not (rho_k > 0); MAX_STEPS), the stop rule on rr and not on rho, alpha * p_i rounded before
+ * the sum, no FMA.  The device evaluates the rules at EVERY step, nothing is written to d_x or to the histories once one has
+ * fired, and no result depends on check_every.
+ * M's symmetry and definiteness are the caller's contract; nothing is validated.  A zero diagonal in a triangle shows as NONFINITE,
+ * an M that is visibly not positive definite as BREAKDOWN.  With first = LOWER / DIAG_STORED and second = UPPER / DIAG_UNIT on a
+ * handle that stores only a diagonal d, and d_m = NULL, every number is smvp_csr_pcg's with m = d, bit for bit: z_i = (r_i - s_i) /
+ * d_i with s_i = +0.0, and r_i - (+0.0) is r_i, a signed zero included.
+ *   - Operands, histories and n == 0 as for smvp_csr_pcg; d_x may be d_x0.  d_m, where given, is n doubles, only read, and must
+ *     not overlap d_x.
+ *   - The call returns after the work on `stream` has finished.  It allocates its workspace per call -- four vectors (r, p, q and
+ *     z: z cannot be re-derived element by element, so it is stored), the partials of three dots, the histories, two status blocks
+ *     -- and frees it on every way out.  Beside the product and the two solves' launches a step is five launches (four without
+ *     d_m) and fifteen passes over a vector (p, q read; q, r read, r written; z, m read, z written; r, z read; x, p, z read, x, p
+ *     written).  No kernel waits on a value another workgroup writes.
+ *   - SMVP_ERR_INVALID for everything smvp_csr_pcg refuses (a NULL d_m excepted), and for: a NULL first or second; a plan whose row
+ *     count is not n or whose device is not the handle's; d_m overlapping d_x; a capturing stream.  SMVP_ERR_UNSUPPORTED as for
+ *     smvp_csr_pcg.  Nothing is enqueued then, d_x and *result are left untouched, and a capturing stream's capture stays valid.
+ *     first == second is allowed.
+ *   - State: the handle as after smvp_csr_pcg / smvp_tjds_pcg.  The plans are used on `stream` for the duration of the call (a
+ *     plan is used by one stream at a time, as ever) and are unchanged afterwards, as are the handles they borrow: smvp_trsv_solve
+ *     gives the bits it gave before.  `val` of either handle changed in place is seen by the next call.
+ * Out of scope: omega inside the library, preconditioned BiCGSTAB, the sharded handles, computing an IC(0) / ILU(0) factorisation,
+ * a block of k right-hand sides. */
+int smvp_csr_pcg_tri(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                     smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
+                     double *rz_each, double *sigma_each, void *stream);
+int smvp_tjds_pcg_tri(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                      smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
+                      double *rz_each, double *sigma_each, void *stream);
 
 /* ------------------------------------------------- BiCGSTAB */
 /* A x = b for a general (non-symmetric) square A on a handle the caller already holds, kernel K13 (new: the reference only

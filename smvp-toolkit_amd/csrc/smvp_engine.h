@@ -204,6 +204,20 @@ int pcg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t
             const double *d_m, smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each, void *stream,
             const HandleProduct &product);
 
+// ------------------------------------------------------- conjugate gradients preconditioned by two triangular solves (K16)
+// smvp_pcg_tri.hip runs K14's steps with z = T2^-1 (m .* (T1^-1 r)) around the same product hook.  The plans are K15's
+// (smvp_trsv.hip): trsv_enqueue is the launch loop smvp_trsv_solve itself goes through, with the operands checked and the plan's
+// device current already; trsv_rows and trsv_device say what a plan was made for.  pcg_tri_check_args makes no HIP call;
+// pcg_tri_run checks the plans, the operands and the stream, then allocates, iterates and frees.
+int trsv_rows(const smvp_trsv_t *t);
+int trsv_device(const smvp_trsv_t *t);
+int trsv_enqueue(const char *fn, smvp_trsv_t *t, const double *d_b, double *d_x, hipStream_t stream);
+int pcg_tri_check_args(const char *fn, const void *h, const smvp_cg_opts_t *opts, const smvp_pcg_result_t *result, const double *d_b,
+                       const smvp_trsv_t *first, const smvp_trsv_t *second);
+int pcg_tri_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0,
+                double *d_x, smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
+                double *rz_each, double *sigma_each, void *stream, const HandleProduct &product);
+
 // ------------------------------------------------------------------------------------------------- BiCGSTAB (K13)
 // smvp_bicgstab.hip runs the steps around the same product hook, two products a step, checked and handed over as for K12.
 int bicgstab_check_args(const char *fn, const void *h, const smvp_bicgstab_opts_t *opts, const smvp_bicgstab_result_t *result,

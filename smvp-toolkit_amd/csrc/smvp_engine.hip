@@ -1007,6 +1007,20 @@ extern "C" int smvp_csr_pcg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const dou
                          stream, [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
 }
 
+// K16 on a CSR handle: the steps are smvp_pcg_tri.hip's, the product is smvp_csr_spmv's on the current plan (which it leaves as it
+// is), the two solves are the caller's plans'
+extern "C" int smvp_csr_pcg_tri(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                                smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
+                                double *rz_each, double *sigma_each, void *stream)
+{
+    if (int rc = smvp::pcg_tri_check_args("smvp_csr_pcg_tri", h, opts, result, d_b, first, second))
+        return rc;
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_pcg_tri: plain CSR handles only (this one belongs to a TJDS matrix)");
+    return smvp::pcg_tri_run("smvp_csr_pcg_tri", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, first, d_m, second, result, rr_each,
+                             rz_each, sigma_each, stream, [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+}
+
 // K14: the diagonal from the handle's own arrays (val is read in place: adopted values changed in place are seen).  No plan, nothing
 // of the handle is written; the group of lanes a row gets follows the mean row length, the VECTOR plan's rule.
 extern "C" int smvp_csr_diagonal(const smvp_csr_t *h, double *d_diag, void *stream)

@@ -438,6 +438,25 @@ extern "C" int smvp_tjds_pcg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const d
                          });
 }
 
+// K16 on a TJDS handle: the steps are smvp_pcg_tri.hip's, the product is K11's, the two solves are the caller's plans' (on CSR
+// handles of their own: a TJDS handle has no triangular solve)
+extern "C" int smvp_tjds_pcg_tri(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                                 smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
+                                 double *rz_each, double *sigma_each, void *stream)
+{
+    if (int rc = smvp::pcg_tri_check_args("smvp_tjds_pcg_tri", h, opts, result, d_b, first, second))
+        return rc;
+    if (!overwrites_y(h))
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_pcg_tri: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
+                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
+    return smvp::pcg_tri_run("smvp_tjds_pcg_tri", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, first, d_m, second, result, rr_each,
+                             rz_each, sigma_each, stream, [h, stream](const double *x, double *y) {
+                                 if (int rc = smvp_tjds_set_x(h, x, stream))
+                                     return rc;
+                                 return smvp_tjds_spmv(h, y, stream);
+                             });
+}
+
 // K14: the diagonal from the handle's own arrays (the true start_pos, not the ref-quirks edit of the plan; val is read in place).  No
 // plan, no x_perm, nothing of the forward product's state is read or written.
 extern "C" int smvp_tjds_diagonal(const smvp_tjds_t *h, double *d_diag, void *stream)

@@ -391,7 +391,16 @@ extern "C" int smvp_trsv_solve(smvp_trsv_t *t, const double *d_b, double *d_x, v
     if (d_b != d_x && operands_overlap(d_b, 1, n, d_x, 1, n, 1))
         return fail(SMVP_ERR_INVALID, "smvp_trsv_solve: the byte ranges of d_b and d_x overlap (d_x may be d_b itself, nothing between)");
     DeviceScope on(t->m.device);
-    hipStream_t st = (hipStream_t)stream;
+    return trsv_enqueue("smvp_trsv_solve", t, d_b, d_x, (hipStream_t)stream);
+}
+
+int smvp::trsv_rows(const smvp_trsv_t *t) { return t->m.rows; }
+int smvp::trsv_device(const smvp_trsv_t *t) { return t->m.device; }
+
+// A solve's launches on `st`, for smvp_trsv_solve and for the solvers that apply a plan inside a step (K16, smvp_pcg_tri.hip): the
+// operands are checked and the plan's device is current already.
+int smvp::trsv_enqueue(const char *fn, smvp_trsv_t *t, const double *d_b, double *d_x, hipStream_t st)
+{
     const int upper = t->uplo == SMVP_TRSV_UPPER, unit = t->diag == SMVP_TRSV_DIAG_UNIT;
     for (const TrsvLaunch &l : t->launches) {
         if (l.chain) {
@@ -412,7 +421,7 @@ extern "C" int smvp_trsv_solve(smvp_trsv_t *t, const double *d_b, double *d_x, v
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-        return fail(SMVP_ERR_HIP, "smvp_trsv_solve: launch failed: %s", hipGetErrorString(e));
+        return fail(SMVP_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
     return SMVP_OK;
 }
 

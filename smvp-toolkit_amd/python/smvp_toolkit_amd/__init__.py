@@ -166,6 +166,7 @@ EXPORTS = [
     "smvp_csr_diagonal", "smvp_tjds_diagonal", "smvp_csr_pcg", "smvp_tjds_pcg",
     "smvp_bicgstab_opts_default", "smvp_csr_bicgstab", "smvp_tjds_bicgstab",
     "smvp_csr_trsv_create", "smvp_trsv_solve", "smvp_trsv_info", "smvp_trsv_schedule", "smvp_trsv_destroy", "smvp_csr_trsv_levels",
+    "smvp_csr_pcg_tri", "smvp_tjds_pcg_tri",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -237,6 +238,8 @@ def lib():
         L.smvp_trsv_destroy.argtypes = [vp]
         L.smvp_trsv_destroy.restype = None
         L.smvp_csr_trsv_levels.argtypes = [ci, vp, vp, ci, vp, C.POINTER(ci)]
+        L.smvp_csr_pcg_tri.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
+        L.smvp_tjds_pcg_tri.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -722,6 +725,23 @@ class TrsvPlan:
             pass
 
 
+def _pcg_tri(fn, handle, b, x, first, second, m, x0, max_steps, tol, check_every, stream):
+    """smvp_csr_pcg_tri / smvp_tjds_pcg_tri -> (PcgResult, rr_each, rz_each, sigma_each), the histories cut to the filled
+    elements.  first and second are open TrsvPlans; m may be None."""
+    for name, t in (("first", first), ("second", second)):
+        if not isinstance(t, TrsvPlan):
+            raise ValueError("%s must be a TrsvPlan, not %s" % (name, type(t).__name__))
+        if not t._t:
+            raise ValueError("%s is a closed TrsvPlan" % name)
+    _device_vectors(b=b, x=x, m=m, x0=x0)
+    o = cg_opts(max_steps, tol, check_every)
+    r = PcgResult()
+    rr, rz, sigma = np.zeros(max(int(max_steps), 0) + 1), np.zeros(max(int(max_steps), 0) + 1), np.zeros(max(int(max_steps), 1))
+    _check(getattr(lib(), fn)(handle, C.byref(o), _dev_ptr(b), _dev_ptr(x0), _dev_ptr(x), first._t, _dev_ptr(m), second._t, C.byref(r),
+                              _p(rr), _p(rz), _p(sigma), _stream_ptr(stream)), fn)
+    return r, rr[:r.updates + 1], rz[:r.updates + 1], sigma[:r.steps]
+
+
 class CsrMatrix:
     """Device-resident CSR matrix (smvp_csr_t).  Arrays may be numpy (copied to HBM) or torch CUDA tensors (adopted)."""
 
@@ -815,6 +835,13 @@ class CsrMatrix:
         """A TrsvPlan for the `uplo` triangle of this matrix as stored (smvp_csr_trsv_create, K15): TRSV_LOWER or TRSV_UPPER,
         the diagonal as stored or taken as ones.  Analysed on the host once; close the plan before the matrix."""
         return TrsvPlan(self, uplo, diag, stream)
+
+    def pcg_tri(self, b, x, first, second, m=None, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Conjugate gradients for A x = b preconditioned with M = T1 diag(m)^-1 T2 (smvp_csr_pcg_tri, K16): z = M^-1 r is
+        first.solve, a multiplication by m (skipped for m=None), second.solve.  first and second are TrsvPlans of any CsrMatrix
+        of `rows` rows on this device -- for symmetric Gauss-Seidel trsv_plan(TRSV_LOWER) and trsv_plan(TRSV_UPPER) of this
+        matrix with m = diagonal().  Operands, stop rule and return value as pcg()."""
+        return _pcg_tri("smvp_csr_pcg_tri", self._h, b, x, first, second, m, x0, max_steps, tol, check_every, stream)
 
     def bicgstab(self, b, x, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
         """BiCGSTAB for A x = b on this handle's product (smvp_csr_bicgstab, K13; A any square matrix): b, x and x0 (None = zeros)
@@ -922,6 +949,12 @@ class TjdsMatrix:
         ROW_GATHER or TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.pcg.  Afterwards the handle's permuted operand is
         the last direction's: call set_x again before the next spmv."""
         return _pcg("smvp_tjds_pcg", self._h, b, x, m, x0, max_steps, tol, check_every, stream)
+
+    def pcg_tri(self, b, x, first, second, m=None, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Conjugate gradients preconditioned with M = T1 diag(m)^-1 T2 on this handle's product in its current mode
+        (smvp_tjds_pcg_tri, K16; ROW_GATHER or TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.pcg_tri.  The
+        TrsvPlans belong to CsrMatrix objects of the same size.  Afterwards call set_x again before the next spmv."""
+        return _pcg_tri("smvp_tjds_pcg_tri", self._h, b, x, first, second, m, x0, max_steps, tol, check_every, stream)
 
     def bicgstab(self, b, x, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
         """BiCGSTAB for A x = b on this handle's product in its current mode (smvp_tjds_bicgstab, K13; ROW_GATHER or TWO_PHASE, no
