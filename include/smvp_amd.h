@@ -69,7 +69,8 @@ const char *smvp_version_string(void); /* "0.6.4" */
  *                            the results are the same bits either way
  *   "tjds_index" 0 | 1 | 2: 16-bit position words (default) / 32-bit sorted / 32-bit columns
  *   "sharded_threads" 1: the sharded layer's issuing threads with one GPU too     "mm_threads" n: the reader's threads (1 = serial)
- *   "trsv_chain_width" 256 | 512 | 1024: the widest level a triangular solve's chain takes (default 256), read by smvp_csr_trsv_create
+ *   "trsv_chain_width" 256 | 512 | 1024: the widest level a triangular solve's chain takes (default 256), read by smvp_csr_trsv_create and
+ *                      smvp_csr_ilu0_create
  *   "trsv_lanes_by_mean" 1: a wide level's lanes per row from the triangle's mean row length alone (default: mean and longest row)
  * Unknown names are SMVP_ERR_INVALID. */
 int smvp_set_option(const char *name, int value);
@@ -699,7 +700,7 @@ int smvp_tjds_diagonal(const smvp_tjds_t *h, double *d_diag, void *stream);
  * nothing is written to x or to the histories.  The host reads a status block at looked steps only -- step 0, every k with
  * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, updates, reason, the three histories and every bit
  * of d_x do not depend on check_every.  A preconditioner made of two triangular solves (symmetric Gauss-Seidel, an incomplete
- * factorisation the caller brings) is smvp_csr_pcg_tri, K16, below.  Preconditioned BiCGSTAB and the sharded handles are out of
+ * factorisation: the caller's, or K17's ILU(0)) is smvp_csr_pcg_tri, K16, below.  Preconditioned BiCGSTAB and the sharded handles are out of
  * scope. */
 typedef struct smvp_pcg_result {
     int steps;   /* products of a direction done (the one for r_0 is not counted) */
@@ -760,7 +761,8 @@ int smvp_tjds_pcg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b,
  *
  * Out of scope: TJDS handles (the format stores by columns: it needs a column-oriented solve), sharded handles, a block of k
  * right-hand sides, the transposed solve T^T x = b (for a symmetric matrix stored in full the other uplo serves) and an analysis
- * on the device.  The solver that uses two plans as a preconditioner is smvp_csr_pcg_tri / smvp_tjds_pcg_tri, K16, below. */
+ * on the device.  The solver that uses two plans as a preconditioner is smvp_csr_pcg_tri / smvp_tjds_pcg_tri, K16, below; the
+ * incomplete factorisation that gives it two triangles on one handle is smvp_csr_ilu0_create, K17, below that. */
 enum { SMVP_TRSV_LOWER = 0, SMVP_TRSV_UPPER = 1 };
 enum { SMVP_TRSV_DIAG_STORED = 0, SMVP_TRSV_DIAG_UNIT = 1 };
 typedef struct smvp_trsv smvp_trsv_t; /* a plan: borrows the handle's arrays, owns level_ptr / order on the device */
@@ -816,6 +818,8 @@ int smvp_csr_trsv_levels(int rows, const int *row_ptr, const int *col_ind, int u
  *     DIAG_STORED on A: M = (D + L) D^-1 (D + U).  The solves skip the other triangle: no extracted copy is needed.
  *   - An incomplete factorisation A ~ F F^T the caller brings: first = LOWER / DIAG_STORED on a handle of F, second = UPPER /
  *     DIAG_STORED on smvp_csr_create_transposed of it, d_m = NULL.
+ *   - An ILU(0) the library computes (smvp_csr_ilu0_create, K17, below): first = LOWER / DIAG_UNIT and second = UPPER /
+ *     DIAG_STORED, both on the factorisation's one handle, d_m = NULL.  No transposed copy is needed.
  *   - SSOR with omega != 1 needs a handle whose diagonal is scaled by 1 / omega (and d_m to match): building it is the caller's
  *     business.
  * Everything else is smvp_csr_pcg's word for word with z = M^-1 r in place of r ./ m: smvp_cg_opts_t, SMVP_CG_*, smvp_pcg_result_t
@@ -841,14 +845,86 @@ int smvp_csr_trsv_levels(int rows, const int *row_ptr, const int *col_ind, int u
  *   - State: the handle as after smvp_csr_pcg / smvp_tjds_pcg.  The plans are used on `stream` for the duration of the call (a
  *     plan is used by one stream at a time, as ever) and are unchanged afterwards, as are the handles they borrow: smvp_trsv_solve
  *     gives the bits it gave before.  `val` of either handle changed in place is seen by the next call.
- * Out of scope: omega inside the library, preconditioned BiCGSTAB, the sharded handles, computing an IC(0) / ILU(0) factorisation,
- * a block of k right-hand sides. */
+ * Out of scope: omega inside the library, preconditioned BiCGSTAB, the sharded handles, a block of k right-hand sides. */
 int smvp_csr_pcg_tri(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                      smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
                      double *rz_each, double *sigma_each, void *stream);
 int smvp_tjds_pcg_tri(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                       smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
                       double *rz_each, double *sigma_each, void *stream);
+
+/* ------------------------------------------------- incomplete LU factorisation, ILU(0) */
+/* A ~ L U on A's own pattern, computed on the device from a plain-CSR handle, kernel K17 (new: the reference only multiplies): the
+ * preconditioner K15 and K16 were built for.  The factor F lives in ONE CSR array on A's row_ptr / col_ind: strictly below the
+ * diagonal L, its unit diagonal implied; on and above the diagonal U.  K15 solves with a triangle of a matrix as stored, stored or
+ * unit diagonal, the other triangle skipped -- so a LOWER / DIAG_UNIT plan and an UPPER / DIAG_STORED plan on F's one handle ARE
+ * M = L U for smvp_csr_pcg_tri / smvp_tjds_pcg_tri with d_m = NULL.
+ * The handle must be plain CSR with first_row == 0 and rows == cols; every row's col_ind must be STRICTLY ASCENDING (sorted, no
+ * repeated column) and every row must store (i, i).  diag_pos[i] is the position of (i, i).  F has values of its own:
+ *   for i = 0 .. n-1, in this order:
+ *     w[p] = val_A[p]                                       for every position p of row i
+ *     for p ascending over row i while col_ind[p] < i:      (the pivots k = col_ind[p], ascending)
+ *       w[p] = w[p] / F[diag_pos[k]]                        one IEEE division by the FINAL u_kk; no reciprocal
+ *       for every position q of row k with col_ind[q] > k:  (q = diag_pos[k] + 1 .. row_ptr[k+1] - 1, final values of row k)
+ *         if row i stores column col_ind[q], at position t (then t > p):
+ *           w[t] = w[t] - w[p] * F[q]                       the product rounded, then the difference rounded: no FMA
+ *     F[p] = w[p]                                           for every position p of row i
+ * Every w[t] gets at most one update per pivot and the pivots come in ascending k, so each element of F has one right answer,
+ * however a row's columns are spread over lanes: the serial loop's, bit for bit, the same on every run.  An update that does not
+ * exist is skipped, its product never formed (0 * Inf would make a NaN).  Pivots are not validated: a zero or vanishing u_kk gives
+ * +-Inf or NaN by the rules above, as d_i does in K15; a caller who wants to know calls smvp_csr_diagonal on F.
+ * Row i reads exactly the rows k < i for which (i, k) is stored: the dependency graph of the LOWER triangular solve.  The schedule,
+ * the launches (wide levels + chains, plan option "trsv_chain_width" as read at create) and the rule are K15's: no kernel waits on
+ * a value another workgroup writes in the same launch -- no flags, no grid barrier, no atomics.
+ * Out of scope: IC(0) as a format of its own, ILU(k) and thresholds, pivoting or diagonal shifts, preconditioned BiCGSTAB (the
+ * obvious follow-up for non-symmetric A), TJDS and sharded handles, an analysis on the device, and coalescing or sorting a matrix
+ * that does not qualify. */
+typedef struct smvp_ilu0 smvp_ilu0_t; /* borrows A's arrays; owns F's values, F's handle, level_ptr / order / diag_pos on the device */
+typedef struct smvp_ilu0_info {
+    unsigned struct_size;  /* set by the caller to sizeof(smvp_ilu0_info_t) before the call; another size is SMVP_ERR_INVALID */
+    int levels;            /* of the LOWER triangle of A's pattern: smvp_trsv_info's for a LOWER plan */
+    int max_level_width;
+    int launches;          /* kernels one factorisation enqueues: wide levels + chains */
+    int chains;
+    int chain_width;
+    int lanes_per_row;     /* lanes a row of a wide level gets (from the mean and the longest row) */
+    long long entries;     /* nnz: values one factorisation reads from A and writes to F */
+    long long pivots;      /* stored entries below the diagonal = divisions */
+    double plan_bytes;     /* device memory the object owns: F's values, level_ptr, order, diag_pos */
+    double build_ms;       /* host wall time of smvp_csr_ilu0_create: copy back, check, analysis, uploads, the first factorisation,
+                              F's handle */
+} smvp_ilu0_info_t;
+/*   - smvp_csr_ilu0_create has smvp_csr_trsv_create's shape and cost: col_ind comes back from the device once, the host runs
+ *     smvp_csr_ilu0_check and K15's LOWER analysis, level_ptr / order / diag_pos go up, F's values (nnz doubles, 16-byte aligned) are
+ *     allocated, the first factorisation runs -- F is valid on return -- and F is made as an ordinary plain-CSR handle that ADOPTS
+ *     h's own d_row_ptr / d_col_ind and the new value array (SMVP_MEM_DEVICE; handles may share arrays).  The call waits for
+ *     `stream`, allocates, and refuses a capturing stream.  h's own state and plans are untouched, and h must outlive f.  Any number
+ *     of factorisations and K15 plans per handle.
+ *   - smvp_ilu0_factor factorises h's CURRENT val again (adopted arrays changed in place; a Newton or time-step loop's new matrix on
+ *     the old pattern).  Asynchronous on `stream`; allocates nothing, synchronises nothing and can be captured from its first call
+ *     on: a plain chain of kernels with no parallel branches.  It reads only A's val, and on return of the work every element of
+ *     F's values has been written anew.  K15 plans made on F earlier see the new factors without any call: they borrow val.  An f
+ *     is used by one stream at a time.
+ *   - smvp_ilu0_matrix: F's handle, BORROWED -- owned and destroyed by f; never pass it to smvp_csr_destroy.  F's own product
+ *     (smvp_csr_spmv on F) follows the rules above for adopted values changed in place, smvp_ilu0_factor being such a change:
+ *     VECTOR / STREAM / STREAM_CARRY and smvp_csr_spmm need nothing, COLSWEEP / BINNED need smvp_csr_set_kernel first.
+ *   - SMVP_ERR_INVALID (nothing enqueued, outputs untouched): a NULL argument, a wrong struct_size, rows != cols, a capturing stream
+ *     at create.  SMVP_ERR_UNSUPPORTED (likewise): a handle that is not plain CSR, a row block, a row whose columns are not strictly
+ *     ascending, a row without a stored diagonal; smvp_last_error names the first offending row and what is wrong with it.
+ *   - n == 0: everything succeeds with 0 levels and 0 launches.
+ *   - smvp_csr_ilu0_check and smvp_csr_ilu0_host are the check and the loop above on HOST arrays, no device touched.  The check
+ *     writes diag_pos (rows ints; may be NULL) and *bad_row = -1 (may be NULL) on success; on refusal diag_pos is untouched and
+ *     *bad_row is the first offending row: SMVP_ERR_INVALID for rows < 0, a NULL row_ptr with rows > 0, a NULL col_ind with entries,
+ *     a row_ptr that is not a non-decreasing sequence from 0, a column outside [0, rows); SMVP_ERR_UNSUPPORTED for columns not
+ *     strictly ascending and for a missing diagonal.  smvp_csr_ilu0_host refuses the same and writes nothing then; val_out (nnz
+ *     doubles) may be val itself.  It is the definition on one core: the only CPU baseline the library has. */
+int smvp_csr_ilu0_create(smvp_ilu0_t **out, const smvp_csr_t *h, void *stream);
+int smvp_ilu0_factor(smvp_ilu0_t *f, void *stream);
+int smvp_ilu0_matrix(const smvp_ilu0_t *f, smvp_csr_t **F);
+int smvp_ilu0_info(const smvp_ilu0_t *f, smvp_ilu0_info_t *out);
+void smvp_ilu0_destroy(smvp_ilu0_t *f);
+int smvp_csr_ilu0_check(int rows, const int *row_ptr, const int *col_ind, int *diag_pos, int *bad_row);
+int smvp_csr_ilu0_host(int rows, const int *row_ptr, const int *col_ind, const double *val, double *val_out);
 
 /* ------------------------------------------------- BiCGSTAB */
 /* A x = b for a general (non-symmetric) square A on a handle the caller already holds, kernel K13 (new: the reference only

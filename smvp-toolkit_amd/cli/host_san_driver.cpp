@@ -1,7 +1,8 @@
 // host_san_driver.cpp -- exercises the host side of libsmvp_amd under sanitizers (make -C smvp-toolkit_amd host-san).
 //
-// Not part of the product: a test driver linked against the eight host translation units only (reader, converters,
-// report writer, cache, CISR export, synthetic generators, the triangular solves' analysis, error text -- no HIP), built with
+// Not part of the product: a test driver linked against the nine host translation units only (reader, converters,
+// report writer, cache, CISR export, synthetic generators, the triangular solves' analysis, the ILU(0) check and host loop, error
+// text -- no HIP), built with
 // g++ -fsanitize=address,undefined and, for the parallel Matrix Market tokeniser, -fsanitize=thread (SURVEY 5,
 // "race detection / sanitizers": the reference has none, CMakeLists.txt:33-34 even comments -Wall out).
 // tests/test_host_sanitizers.py runs it over the reference's sample files, malformed inputs, crafted cache files.
@@ -17,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 static int g_bad = 0;
@@ -245,6 +247,46 @@ static int run_synth(const std::string &tmp)
     printf("five refused trsv analyses: rc sum %d\n", rc);
     if (rc != 5 * SMVP_ERR_INVALID)
         ++g_bad;
+    // ---- K17's host side (smvp_ilu0_plan.cpp): the check and the serial factorisation on a small matrix, empty input, refusals
+    {
+        const std::vector<int> rp3{0, 2, 5, 7}, ci3{0, 1, 0, 1, 2, 1, 2};  // [[4, 2, 0], [2, 5, 2], [0, 2, 2]]
+        const std::vector<double> v3{4, 2, 2, 5, 2, 2, 2}, want{4, 2, 0.5, 4, 2, 0.5, 1};
+        std::vector<int> dp(3, -1);
+        std::vector<double> f3(7, -1.0);
+        int bad = 7;
+        MUST(smvp_csr_ilu0_check(3, rp3.data(), ci3.data(), dp.data(), &bad));
+        MUST(smvp_csr_ilu0_check(3, rp3.data(), ci3.data(), nullptr, nullptr));
+        MUST(smvp_csr_ilu0_host(3, rp3.data(), ci3.data(), v3.data(), f3.data()));
+        if (bad != -1 || dp != std::vector<int>{0, 3, 6} || f3 != want)
+            ++g_bad, fprintf(stderr, "FAILED: the 3 x 3 ILU(0): bad_row %d, diag_pos %d %d %d\n", bad, dp[0], dp[1], dp[2]);
+        std::vector<double> in_place(v3);
+        MUST(smvp_csr_ilu0_host(3, rp3.data(), ci3.data(), in_place.data(), in_place.data()));
+        if (in_place != want)
+            ++g_bad, fprintf(stderr, "FAILED: the 3 x 3 ILU(0) in place\n");
+        MUST(smvp_csr_ilu0_check(0, rp1.data(), nullptr, nullptr, &bad));
+        MUST(smvp_csr_ilu0_host(0, nullptr, nullptr, nullptr, nullptr));
+        // the bidiagonal chain above stores (i, i) before (i, i - 1): not ascending, refused at row 1; then the same rows sorted
+        int rc17 = smvp_csr_ilu0_check(n, chain_rp.data(), chain_c.data(), chain_lv.data(), &bad);
+        if (rc17 != SMVP_ERR_UNSUPPORTED || bad != 1)
+            ++g_bad, fprintf(stderr, "FAILED: the unsorted chain: rc %d, bad_row %d\n", rc17, bad);
+        for (int i = 1; i < n; ++i)
+            std::swap(chain_c[(size_t)chain_rp[(size_t)i]], chain_c[(size_t)chain_rp[(size_t)i] + 1]);
+        std::vector<double> cv(chain_c.size(), 0.25), cf(chain_c.size());
+        for (int i = 0; i < n; ++i)
+            cv[(size_t)chain_rp[(size_t)i + 1] - 1] = 2.0;  // the diagonal stands last in every row
+        MUST(smvp_csr_ilu0_host(n, chain_rp.data(), chain_c.data(), cv.data(), cf.data()));
+        if (cf[0] != 2.0 || cf[1] != 0.125 || cf[2] != 2.0)  // (row 0 stores no column 1: nothing is subtracted from u_11)
+            ++g_bad, fprintf(stderr, "FAILED: the sorted chain's factor begins %g %g %g\n", cf[0], cf[1], cf[2]);
+        std::vector<int> no_diag{0, 1, 0, 1, 2, 0, 1}, past{0, 1, 0, 1, 3, 1, 2}, falling{0, 5, 2, 7};
+        rc17 = smvp_csr_ilu0_check(3, rp3.data(), no_diag.data(), dp.data(), &bad) == SMVP_ERR_UNSUPPORTED && bad == 2;
+        rc17 += smvp_csr_ilu0_host(3, rp3.data(), past.data(), v3.data(), f3.data()) == SMVP_ERR_INVALID;
+        rc17 += smvp_csr_ilu0_check(3, falling.data(), ci3.data(), dp.data(), &bad) == SMVP_ERR_INVALID && bad == 1;
+        rc17 += smvp_csr_ilu0_check(-1, nullptr, nullptr, nullptr, nullptr) == SMVP_ERR_INVALID;
+        rc17 += smvp_csr_ilu0_host(3, rp3.data(), ci3.data(), nullptr, f3.data()) == SMVP_ERR_INVALID;
+        printf("five refused ILU(0) calls: %d as expected\n", rc17);
+        if (rc17 != 5 || dp != std::vector<int>{0, 3, 6} || f3 != want)
+            ++g_bad, fprintf(stderr, "FAILED: a refused ILU(0) call wrote its outputs\n");
+    }
     printf("version %s\n", smvp_version_string());
     return 0;
 }

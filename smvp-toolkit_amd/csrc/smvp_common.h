@@ -30,6 +30,10 @@ struct TrsvLaunch {
 };
 int trsv_analyse(int rows, const int *row_ptr, const int *col_ind, int uplo, TrsvSchedule *out);
 void trsv_launches(const std::vector<int> &level_ptr, int chain_width, std::vector<TrsvLaunch> *out, int *chains);
+
+// K17, what an ILU(0) asks of a CSR pattern (smvp_ilu0_plan.cpp): smvp_csr_ilu0_check under the caller's name `fn`, the arguments
+// checked for null already
+int ilu0_check(const char *fn, int rows, const int *row_ptr, const int *col_ind, int *diag_pos, int *bad_row);
 }  // namespace smvp
 
 // internal, device side (smvp_convert_device.hip): see its definition

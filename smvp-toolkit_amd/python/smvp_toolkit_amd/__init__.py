@@ -123,6 +123,12 @@ class TrsvInfo(C.Structure):
                 ("plan_bytes", C.c_double), ("build_ms", C.c_double)]
 
 
+class Ilu0Info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("levels", C.c_int), ("max_level_width", C.c_int), ("launches", C.c_int), ("chains", C.c_int),
+                ("chain_width", C.c_int), ("lanes_per_row", C.c_int), ("entries", C.c_longlong), ("pivots", C.c_longlong),
+                ("plan_bytes", C.c_double), ("build_ms", C.c_double)]
+
+
 POWER_CONVERGED, POWER_MAX_STEPS, POWER_ZERO, POWER_NONFINITE = 0, 1, 2, 3
 TRSV_LOWER, TRSV_UPPER = 0, 1
 TRSV_DIAG_STORED, TRSV_DIAG_UNIT = 0, 1
@@ -167,6 +173,8 @@ EXPORTS = [
     "smvp_bicgstab_opts_default", "smvp_csr_bicgstab", "smvp_tjds_bicgstab",
     "smvp_csr_trsv_create", "smvp_trsv_solve", "smvp_trsv_info", "smvp_trsv_schedule", "smvp_trsv_destroy", "smvp_csr_trsv_levels",
     "smvp_csr_pcg_tri", "smvp_tjds_pcg_tri",
+    "smvp_csr_ilu0_create", "smvp_ilu0_factor", "smvp_ilu0_matrix", "smvp_ilu0_info", "smvp_ilu0_destroy", "smvp_csr_ilu0_check",
+    "smvp_csr_ilu0_host",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -240,6 +248,14 @@ def lib():
         L.smvp_csr_trsv_levels.argtypes = [ci, vp, vp, ci, vp, C.POINTER(ci)]
         L.smvp_csr_pcg_tri.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
         L.smvp_tjds_pcg_tri.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
+        L.smvp_csr_ilu0_create.argtypes = [C.POINTER(vp), vp, vp]
+        L.smvp_ilu0_factor.argtypes = [vp, vp]
+        L.smvp_ilu0_matrix.argtypes = [vp, C.POINTER(vp)]
+        L.smvp_ilu0_info.argtypes = [vp, C.POINTER(Ilu0Info)]
+        L.smvp_ilu0_destroy.argtypes = [vp]
+        L.smvp_ilu0_destroy.restype = None
+        L.smvp_csr_ilu0_check.argtypes = [ci, vp, vp, vp, C.POINTER(ci)]
+        L.smvp_csr_ilu0_host.argtypes = [ci, vp, vp, vp, vp]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -742,6 +758,77 @@ def _pcg_tri(fn, handle, b, x, first, second, m, x0, max_steps, tol, check_every
     return r, rr[:r.updates + 1], rz[:r.updates + 1], sigma[:r.steps]
 
 
+def ilu0_check(rows, row_ptr, col_ind):
+    """diag_pos, the position of every row's (i, i), for CSR arrays on the host that admit an ILU(0) (smvp_csr_ilu0_check, K17):
+    every row's columns strictly ascending, a stored diagonal in every row.  Raises SmvpError otherwise; its bad_row attribute is the
+    first offending row."""
+    rp, ci = _arr(row_ptr, np.int32), _arr(col_ind, np.int32)
+    diag_pos = np.zeros(max(int(rows), 1), dtype=np.int32)
+    bad = C.c_int(-1)
+    code = lib().smvp_csr_ilu0_check(int(rows), _p(rp), _p(ci), _p(diag_pos), C.byref(bad))
+    if code != OK:
+        e = SmvpError(code, "smvp_csr_ilu0_check")
+        e.bad_row = bad.value
+        raise e
+    return diag_pos[:max(int(rows), 0)]
+
+
+def ilu0_host(rows, row_ptr, col_ind, val):
+    """The values of the ILU(0) factor of CSR arrays on the host, by the serial loop of the header on one core
+    (smvp_csr_ilu0_host, K17): what every element of Ilu0.matrix's values is, bit for bit."""
+    rp, ci, v = _arr(row_ptr, np.int32), _arr(col_ind, np.int32), _arr(val, np.float64)
+    nnz = int(rp[rows]) if rows > 0 else 0
+    out = np.zeros(max(nnz, 1), dtype=np.float64)
+    _check(lib().smvp_csr_ilu0_host(int(rows), _p(rp), _p(ci), _p(v), _p(out)), "smvp_csr_ilu0_host")
+    return out[:nnz]
+
+
+class Ilu0:
+    """An ILU(0) of a CsrMatrix on its own pattern (smvp_ilu0_t, K17).  `matrix` is the factor as a CsrMatrix over a handle this
+    object owns: strictly below the diagonal L (unit diagonal implied), on and above it U.  It borrows the CsrMatrix's device arrays
+    and keeps a reference to it; `matrix` in turn keeps this object alive, so plans made on it (which keep `matrix`) may outlive
+    the caller's own reference to the Ilu0: `L, U = A.ilu0().plans()` is safe.  close() ends that: close the plans first."""
+
+    def __init__(self, matrix, stream=None):
+        self._f = C.c_void_p()
+        self.source, self.rows = matrix, matrix.rows
+        _check(lib().smvp_csr_ilu0_create(C.byref(self._f), matrix._h, _stream_ptr(stream)), "smvp_csr_ilu0_create")
+        h = C.c_void_p()
+        _check(lib().smvp_ilu0_matrix(self._f, C.byref(h)), "smvp_ilu0_matrix")
+        self.matrix = CsrMatrix._wrap(h, matrix.rows, matrix.cols, matrix.nnz, owner=self)
+
+    def factor(self, stream=None):
+        """Factorises the source matrix's current values again, asynchronous on `stream`; plans made on `matrix` see the new
+        factors.  Returns self."""
+        _check(lib().smvp_ilu0_factor(self._f, _stream_ptr(stream)), "smvp_ilu0_factor")
+        return self
+
+    def info(self):
+        """smvp_ilu0_info_t as a dict."""
+        i = Ilu0Info()
+        i.struct_size = C.sizeof(Ilu0Info)
+        _check(lib().smvp_ilu0_info(self._f, C.byref(i)), "smvp_ilu0_info")
+        return {name: getattr(i, name) for name, _ in Ilu0Info._fields_[1:]}
+
+    def plans(self, stream=None):
+        """(first, second) for pcg_tri with m=None: the LOWER / DIAG_UNIT and the UPPER / DIAG_STORED TrsvPlan of `matrix`.
+        Close them before this object."""
+        return (self.matrix.trsv_plan(TRSV_LOWER, TRSV_DIAG_UNIT, stream), self.matrix.trsv_plan(TRSV_UPPER, TRSV_DIAG_STORED, stream))
+
+    def close(self):
+        if self._f:
+            lib().smvp_ilu0_destroy(self._f)
+            self._f = C.c_void_p()
+            self.matrix._h = C.c_void_p()                    # (the borrowed handle went with it)
+            self.matrix._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CsrMatrix:
     """Device-resident CSR matrix (smvp_csr_t).  Arrays may be numpy (copied to HBM) or torch CUDA tensors (adopted)."""
 
@@ -868,12 +955,20 @@ class CsrMatrix:
         return name.value.decode(), b.value, {"plan_bytes": i.plan_bytes, "build_ms": i.build_ms}
 
     @classmethod
-    def _wrap(cls, handle, rows, cols, nnz):
-        """A CsrMatrix over a handle the library made itself (it owns its arrays)."""
+    def _wrap(cls, handle, rows, cols, nnz, owner=None):
+        """A CsrMatrix over a handle the library made itself (it owns its arrays).  owner: the object the handle belongs to (an
+        Ilu0 and its factor) -- close() then destroys nothing, and the wrapper keeps the owner alive as long as it lives itself."""
         m = cls.__new__(cls)
         m.rows, m.cols, m.nnz = rows, cols, nnz
-        m._h, m._keep = handle, None
+        m._h, m._keep = handle, owner
+        m._borrowed = owner is not None
         return m
+
+    def ilu0(self, stream=None):
+        """The ILU(0) of this matrix on its own pattern (smvp_csr_ilu0_create, K17) as an Ilu0: every row's columns must be
+        strictly ascending and every row must store its diagonal.  Returns after the first factorisation has finished; close the
+        Ilu0 before the matrix."""
+        return Ilu0(self, stream)
 
     def transposed(self, stream=None):
         """A^T as a CsrMatrix of its own (smvp_csr_create_transposed): cols x rows, built on the device, independent of this
@@ -889,7 +984,7 @@ class CsrMatrix:
         return rp.value or 0, ci.value or 0, v.value or 0
 
     def close(self):
-        if self._h:
+        if self._h and not getattr(self, "_borrowed", False):
             lib().smvp_csr_destroy(self._h)
             self._h = C.c_void_p()
 
