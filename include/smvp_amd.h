@@ -700,8 +700,8 @@ int smvp_tjds_diagonal(const smvp_tjds_t *h, double *d_diag, void *stream);
  * nothing is written to x or to the histories.  The host reads a status block at looked steps only -- step 0, every k with
  * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, updates, reason, the three histories and every bit
  * of d_x do not depend on check_every.  A preconditioner made of two triangular solves (symmetric Gauss-Seidel, an incomplete
- * factorisation: the caller's, or K17's ILU(0)) is smvp_csr_pcg_tri, K16, below.  Preconditioned BiCGSTAB and the sharded handles are out of
- * scope. */
+ * factorisation: the caller's, or K17's ILU(0)) is smvp_csr_pcg_tri, K16, below.  Preconditioned BiCGSTAB is smvp_csr_pbicgstab, K18,
+ * further below; the sharded handles are out of scope. */
 typedef struct smvp_pcg_result {
     int steps;   /* products of a direction done (the one for r_0 is not counted) */
     int updates; /* updates of x done: steps, or steps - 1 after rule A */
@@ -845,7 +845,8 @@ int smvp_csr_trsv_levels(int rows, const int *row_ptr, const int *col_ind, int u
  *   - State: the handle as after smvp_csr_pcg / smvp_tjds_pcg.  The plans are used on `stream` for the duration of the call (a
  *     plan is used by one stream at a time, as ever) and are unchanged afterwards, as are the handles they borrow: smvp_trsv_solve
  *     gives the bits it gave before.  `val` of either handle changed in place is seen by the next call.
- * Out of scope: omega inside the library, preconditioned BiCGSTAB, the sharded handles, a block of k right-hand sides. */
+ * Out of scope: omega inside the library, the sharded handles, a block of k right-hand sides.  BiCGSTAB preconditioned by the same
+ * M, for a matrix that is not symmetric, is smvp_csr_pbicgstab, K18, below. */
 int smvp_csr_pcg_tri(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                      smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
                      double *rz_each, double *sigma_each, void *stream);
@@ -876,9 +877,9 @@ int smvp_tjds_pcg_tri(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *
  * Row i reads exactly the rows k < i for which (i, k) is stored: the dependency graph of the LOWER triangular solve.  The schedule,
  * the launches (wide levels + chains, plan option "trsv_chain_width" as read at create) and the rule are K15's: no kernel waits on
  * a value another workgroup writes in the same launch -- no flags, no grid barrier, no atomics.
- * Out of scope: IC(0) as a format of its own, ILU(k) and thresholds, pivoting or diagonal shifts, preconditioned BiCGSTAB (the
- * obvious follow-up for non-symmetric A), TJDS and sharded handles, an analysis on the device, and coalescing or sorting a matrix
- * that does not qualify. */
+ * Out of scope: IC(0) as a format of its own, ILU(k) and thresholds, pivoting or diagonal shifts, TJDS and sharded handles, an
+ * analysis on the device, and coalescing or sorting a matrix that does not qualify.  The solver that uses the two plans for a
+ * non-symmetric A is smvp_csr_pbicgstab / smvp_tjds_pbicgstab, K18, below. */
 typedef struct smvp_ilu0 smvp_ilu0_t; /* borrows A's arrays; owns F's values, F's handle, level_ptr / order / diag_pos on the device */
 typedef struct smvp_ilu0_info {
     unsigned struct_size;  /* set by the caller to sizeof(smvp_ilu0_info_t) before the call; another size is SMVP_ERR_INVALID */
@@ -965,7 +966,8 @@ int smvp_csr_ilu0_host(int rows, const int *row_ptr, const int *col_ind, const d
  * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, full, half, reason, rr, both histories and every bit
  * of d_x do not depend on check_every (which decides how many products are enqueued in vain, and how often the host waits), exactly
  * as for conjugate gradients.
- * Preconditioning, restarts, a true-residual check and the sharded handles are out of scope. */
+ * Restarts, a true-residual check and the sharded handles are out of scope.  Preconditioning is smvp_csr_pbicgstab /
+ * smvp_tjds_pbicgstab, K18, below. */
 enum { SMVP_BICGSTAB_CONVERGED = 0, SMVP_BICGSTAB_MAX_STEPS = 1, SMVP_BICGSTAB_BREAKDOWN = 2, SMVP_BICGSTAB_NONFINITE = 3 };
 typedef struct smvp_bicgstab_opts {
     unsigned struct_size; /* set by smvp_bicgstab_opts_default, checked as for smvp_cg_opts_t */
@@ -1008,6 +1010,89 @@ int smvp_csr_bicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts, const dou
                       smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream);
 int smvp_tjds_bicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                        smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream);
+
+/* ------------------------------------------------- preconditioned BiCGSTAB */
+/* Right-preconditioned BiCGSTAB on a square n x n handle's own product, kernel K18 (new: the reference only multiplies): BiCGSTAB
+ * above with K16's M = T1 diag(m)^-1 T2, the solver ILU(0) (K17) was missing for a matrix that is not symmetric.  smvp_bicgstab_opts_t,
+ * smvp_bicgstab_result_t and SMVP_BICGSTAB_* are K13's, unchanged.  `first` and `second` are plans of smvp_csr_trsv_create on ANY
+ * plain-CSR handle of n rows on the handle's device; the product may be a CSR or a TJDS handle's.  Write yhat = M^-1 y for
+ *   w   = T1^-1 y      smvp_trsv_solve(first, y, yhat): K15's bits;  w = y when first == NULL
+ *   w_i = m_i * w_i    one rounded multiplication; skipped entirely when d_m == NULL
+ *   yhat = T2^-1 w     smvp_trsv_solve(second, ...), in place on w;  yhat = w when second == NULL
+ * Each of first, d_m and second may be NULL on its own; all three NULL is SMVP_ERR_INVALID (that run is smvp_csr_bicgstab's).
+ *   - Jacobi: first = second = NULL, d_m = 1 ./ diagonal (smvp_csr_diagonal / smvp_tjds_diagonal and one reciprocal, the caller's):
+ *     one multiplication, no plan and no CSR copy, so it works from a TJDS handle too.
+ *   - ILU(0): first = LOWER / DIAG_UNIT and second = UPPER / DIAG_STORED on smvp_ilu0_matrix, d_m = NULL.
+ *   - Symmetric Gauss-Seidel: first = LOWER / DIAG_STORED and second = UPPER / DIAG_STORED on A itself, d_m = smvp_csr_diagonal of
+ *     A: M = (D + L) D^-1 (D + U), no extracted copy.
+ * `dot` is the one above; every other operation is one correctly rounded IEEE operation per element, no FMA, every product rounded
+ * before its sum: every number below is a pure function of the handle's single products and K15's solves.
+ *   bb = dot(b, b)        thr = (tol * tol) * bb      (tol * tol rounded on the host, the product on the device)
+ *   x_0 = d_x0, or zeros if NULL
+ *   r_0 = b - A x_0       (d_x0 == NULL: r_0 = b bit for bit, no product is run)
+ *   rhat = r_0  (kept for the whole run)      p_0 = r_0      rho_0 = rr_0 = dot(r_0, r_0)
+ *   step 0 rule:  NONFINITE if bb or rr_0 is NaN or +-Inf;  CONVERGED if rr_0 <= thr      (M is not applied at step 0's rule)
+ *   step k = 1, 2, ...:
+ *     phat  = M^-1 p_{k-1}
+ *     v     = A phat                         the handle's own product, bit for bit, as for K13
+ *     sigma = dot(rhat, v)
+ *     rule A:  NONFINITE if sigma is NaN or +-Inf;  BREAKDOWN if sigma == 0               -> x stays x_{k-1}, half = 0
+ *     alpha = rho_{k-1} / sigma
+ *     s     = r_{k-1} - alpha * v            (alpha * v_i rounded, then the difference rounded)
+ *     ss    = dot(s, s)
+ *     rule H:  NONFINITE if ss is NaN or +-Inf                                             -> x stays x_{k-1}, half = 0
+ *              CONVERGED if ss <= thr                                                      -> x = x_{k-1} + alpha * phat, half = 1
+ *     shat  = M^-1 s
+ *     t     = A shat                         the handle's own product
+ *     ts = dot(t, s)      tt = dot(t, t)
+ *     rule T:  NONFINITE if ts or tt is NaN or +-Inf                                       -> x stays x_{k-1}, half = 0
+ *              BREAKDOWN if not (tt > 0)                                                   -> x = x_{k-1} + alpha * phat, half = 1
+ *     omega = ts / tt
+ *     x_k = (x_{k-1} + alpha * phat) + omega * shat      (each product rounded; the additions in this order)
+ *     r_k = s - omega * t
+ *     rr_k = dot(r_k, r_k)      rho_k = dot(rhat, r_k)
+ *     rule B (the first that holds):  NONFINITE if rr_k or rho_k is NaN or +-Inf;  CONVERGED if rr_k <= thr;
+ *              MAX_STEPS if k == max_steps;  BREAKDOWN if omega == 0 or rho_k == 0        -> x = x_k, half = 0, full = k
+ *     beta = (rho_k / rho_{k-1}) * (alpha / omega)       (two quotients rounded, then their product)
+ *     p_k  = r_k + beta * (p_{k-1} - omega * v)          (four roundings, as for K13)
+ * No square root is taken.  With right preconditioning r is the recurrence's residual of the ORIGINAL system, so the stop rule
+ * stays rr <= thr: smvp_csr_bicgstab can be swapped for smvp_csr_pbicgstab under the same tol.  The two differ from b - A x by
+ * rounding, and no true-residual check is made.  Nothing of M is validated: a zero stored diagonal in a triangle, or a NaN in m,
+ * shows as NONFINITE by rule A.
+ * The device evaluates the rules at EVERY step; the first that holds, in the order written, is the `reason`, and from then on
+ * nothing is written to x or to the histories.  The host reads a status block at looked steps only -- step 0, every k with
+ * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, full, half, reason, rr, both histories and every bit
+ * of d_x do not depend on check_every.  A step enqueued in vain runs both products and up to four solves: with plans, a caller wants
+ * a small check_every.
+ * Two identities follow, and the tests hold the device to both.  With first = LOWER / DIAG_STORED and second = UPPER / DIAG_UNIT on a
+ * handle that stores only a unit diagonal, and d_m = NULL, every number is smvp_csr_bicgstab's, bit for bit: (y_i - (+0.0)) / 1.0 is
+ * y_i, a signed zero included.  The same holds with both plans NULL and d_m all ones.
+ *   - Operands, histories and n == 0 as for smvp_csr_bicgstab; d_x may be d_x0.  d_m, where given, is n doubles, only read, and must
+ *     not overlap d_x.
+ *   - The call returns after the work on `stream` has finished.  It allocates its workspace per call -- seven vectors (r, p, v, t,
+ *     rhat, phat, shat), the partials of six dots, four words, the histories, two status blocks -- and frees it on every way out.
+ *     Beside the two products and the solves' own launches a step is five launches and nineteen passes over a vector: rhat, v read;
+ *     v, r read, s written over r; t, s read; x, phat, shat, s, t, rhat read, x, r written; r, p, v read, p written.  Without a
+ *     `first` the multiplication by m costs no launch: the kernel that writes p (or s) reads m and writes phat (or shat) in the same
+ *     pass -- Jacobi is five launches and 23 passes -- and `second` then solves in place on that.  With a `first` it is a launch of
+ *     its own between the solves, as in K16.  With neither `first` nor d_m, `second` solves straight from p or s.  The bits are
+ *     the same either way.  No kernel waits on a value another workgroup writes; no atomics, no flags.
+ *   - SMVP_ERR_INVALID for everything smvp_csr_bicgstab refuses, and for: first, d_m and second all NULL; a plan whose row count is
+ *     not n or whose device is not the handle's; d_m overlapping d_x; a capturing stream.  SMVP_ERR_UNSUPPORTED as for
+ *     smvp_csr_bicgstab.  Nothing is enqueued then, d_x and *result are left untouched, and a capturing stream's capture stays valid.
+ *     first == second is allowed.
+ *   - State: the handle as after smvp_csr_bicgstab / smvp_tjds_bicgstab.  The plans are used on `stream` for the duration of the
+ *     call (a plan is used by one stream at a time, as ever) and are unchanged afterwards, as are the handles they borrow:
+ *     smvp_trsv_solve gives the bits it gave before.  `val` of either handle changed in place (smvp_ilu0_factor is such a change)
+ *     is seen by the next call.
+ * Out of scope: left or split preconditioning, restarts and a true-residual check, a block of k right-hand sides, the sharded
+ * handles, and building the reciprocal diagonal (one reciprocal of smvp_csr_diagonal's output, the caller's). */
+int smvp_csr_pbicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                       smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_bicgstab_result_t *result, double *rr_each,
+                       double *ss_each, void *stream);
+int smvp_tjds_pbicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                        smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_bicgstab_result_t *result, double *rr_each,
+                        double *ss_each, void *stream);
 
 /* ------------------------------------------- several GPUs, one host process */
 /* New design (the reference is one CPU thread): the matrix is cut into `ngpus` row blocks balanced by entries

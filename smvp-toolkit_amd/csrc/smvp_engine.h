@@ -225,4 +225,14 @@ int bicgstab_check_args(const char *fn, const void *h, const smvp_bicgstab_opts_
 int bicgstab_run(const char *fn, int device, int rows, int cols, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0,
                  double *d_x, smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream, const HandleProduct &product);
 
+// ---------------------------------------------------------------------------------- preconditioned BiCGSTAB (K18)
+// smvp_pbicgstab.hip runs K13's steps with phat = M^-1 p and shat = M^-1 s, M = T1 diag(m)^-1 T2 as in K16 with each part optional,
+// around the same product hook and K15's trsv_enqueue.  pbicgstab_check_args is K13's plus "not all three NULL" and makes no HIP
+// call; pbicgstab_run checks the plans, the operands and the stream, then allocates, iterates and frees.
+int pbicgstab_check_args(const char *fn, const void *h, const smvp_bicgstab_opts_t *opts, const smvp_bicgstab_result_t *result,
+                         const double *d_b, const smvp_trsv_t *first, const double *d_m, const smvp_trsv_t *second);
+int pbicgstab_run(const char *fn, int device, int rows, int cols, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0,
+                  double *d_x, smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_bicgstab_result_t *result,
+                  double *rr_each, double *ss_each, void *stream, const HandleProduct &product);
+
 }  // namespace smvp

@@ -1055,6 +1055,20 @@ extern "C" int smvp_csr_bicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts
                               [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
 }
 
+// K18 on a CSR handle: the steps are smvp_pbicgstab.hip's, both products smvp_csr_spmv's on the current plan (which they leave as it
+// is), the solves are the caller's plans'
+extern "C" int smvp_csr_pbicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                                  smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_bicgstab_result_t *result,
+                                  double *rr_each, double *ss_each, void *stream)
+{
+    if (int rc = smvp::pbicgstab_check_args("smvp_csr_pbicgstab", h, opts, result, d_b, first, d_m, second))
+        return rc;
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_pbicgstab: plain CSR handles only (this one belongs to a TJDS matrix)");
+    return smvp::pbicgstab_run("smvp_csr_pbicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, first, d_m, second, result, rr_each,
+                               ss_each, stream, [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+}
+
 // the owner kernel, whose launch can time itself on the device?
 int smvp::csr_stamp_slots(const smvp_csr_t *h)
 {

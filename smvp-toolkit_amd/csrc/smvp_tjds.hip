@@ -489,6 +489,25 @@ extern "C" int smvp_tjds_bicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *op
                               });
 }
 
+// K18 on a TJDS handle: the steps are smvp_pbicgstab.hip's, both products K11's, the solves are the caller's plans' (on CSR handles
+// of their own: a TJDS handle has no triangular solve; Jacobi needs none)
+extern "C" int smvp_tjds_pbicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                                   smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_bicgstab_result_t *result,
+                                   double *rr_each, double *ss_each, void *stream)
+{
+    if (int rc = smvp::pbicgstab_check_args("smvp_tjds_pbicgstab", h, opts, result, d_b, first, d_m, second))
+        return rc;
+    if (!overwrites_y(h))
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_pbicgstab: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
+                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
+    return smvp::pbicgstab_run("smvp_tjds_pbicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, first, d_m, second, result, rr_each,
+                               ss_each, stream, [h, stream](const double *x, double *y) {
+                                   if (int rc = smvp_tjds_set_x(h, x, stream))
+                                       return rc;
+                                   return smvp_tjds_spmv(h, y, stream);
+                               });
+}
+
 // the row-gather product (which overwrites y) through the owner kernel of `rg`, on the operand of smvp_tjds_set_x
 int smvp::tjds_stamp_slots(const smvp_tjds_t *h)
 {

@@ -173,6 +173,7 @@ EXPORTS = [
     "smvp_bicgstab_opts_default", "smvp_csr_bicgstab", "smvp_tjds_bicgstab",
     "smvp_csr_trsv_create", "smvp_trsv_solve", "smvp_trsv_info", "smvp_trsv_schedule", "smvp_trsv_destroy", "smvp_csr_trsv_levels",
     "smvp_csr_pcg_tri", "smvp_tjds_pcg_tri",
+    "smvp_csr_pbicgstab", "smvp_tjds_pbicgstab",
     "smvp_csr_ilu0_create", "smvp_ilu0_factor", "smvp_ilu0_matrix", "smvp_ilu0_info", "smvp_ilu0_destroy", "smvp_csr_ilu0_check",
     "smvp_csr_ilu0_host",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
@@ -248,6 +249,8 @@ def lib():
         L.smvp_csr_trsv_levels.argtypes = [ci, vp, vp, ci, vp, C.POINTER(ci)]
         L.smvp_csr_pcg_tri.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
         L.smvp_tjds_pcg_tri.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
+        L.smvp_csr_pbicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
+        L.smvp_tjds_pbicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
         L.smvp_csr_ilu0_create.argtypes = [C.POINTER(vp), vp, vp]
         L.smvp_ilu0_factor.argtypes = [vp, vp]
         L.smvp_ilu0_matrix.argtypes = [vp, C.POINTER(vp)]
@@ -758,6 +761,28 @@ def _pcg_tri(fn, handle, b, x, first, second, m, x0, max_steps, tol, check_every
     return r, rr[:r.updates + 1], rz[:r.updates + 1], sigma[:r.steps]
 
 
+def _pbicgstab(fn, handle, b, x, first, second, m, x0, max_steps, tol, check_every, stream):
+    """smvp_csr_pbicgstab / smvp_tjds_pbicgstab -> (BicgstabResult, rr_each, ss_each), the histories cut to the filled elements as
+    _bicgstab cuts them.  first and second are open TrsvPlans or None; m may be None (all three None is the library's refusal)."""
+    for name, t in (("first", first), ("second", second)):
+        if t is None:
+            continue
+        if not isinstance(t, TrsvPlan):
+            raise ValueError("%s must be a TrsvPlan or None, not %s" % (name, type(t).__name__))
+        if not t._t:
+            raise ValueError("%s is a closed TrsvPlan" % name)
+    _device_vectors(b=b, x=x, m=m, x0=x0)
+    o = bicgstab_opts(max_steps, tol, check_every)
+    r = BicgstabResult()
+    rr, ss = np.zeros(max(int(max_steps), 0) + 1), np.full(max(int(max_steps), 1), -0.0)
+    _check(getattr(lib(), fn)(handle, C.byref(o), _dev_ptr(b), _dev_ptr(x0), _dev_ptr(x), first._t if first else None, _dev_ptr(m),
+                              second._t if second else None, C.byref(r), _p(rr), _p(ss), _stream_ptr(stream)), fn)
+    filled = r.steps
+    if filled > 0 and ss[filled - 1] == 0.0 and np.signbit(ss[filled - 1]):
+        filled -= 1
+    return r, rr[:r.full + 1], ss[:filled]
+
+
 def ilu0_check(rows, row_ptr, col_ind):
     """diag_pos, the position of every row's (i, i), for CSR arrays on the host that admit an ILU(0) (smvp_csr_ilu0_check, K17):
     every row's columns strictly ascending, a stored diagonal in every row.  Raises SmvpError otherwise; its bad_row attribute is the
@@ -937,6 +962,14 @@ class CsrMatrix:
         norm of s of every step that got as far.  Nothing depends on check_every but how often the host waits."""
         return _bicgstab("smvp_csr_bicgstab", self._h, b, x, x0, max_steps, tol, check_every, stream)
 
+    def pbicgstab(self, b, x, first=None, second=None, m=None, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Right-preconditioned BiCGSTAB for A x = b with M = T1 diag(m)^-1 T2 (smvp_csr_pbicgstab, K18; A any square matrix):
+        first and second are TrsvPlans of any CsrMatrix with as many rows, m a float64 CUDA tensor, each of the three optional but
+        not all None.  m = 1 / diagonal() alone is Jacobi; ilu0().plans() is ILU(0); the LOWER and UPPER / STORED plans of this
+        matrix with m = diagonal() are symmetric Gauss-Seidel.  Operands and result as bicgstab: (BicgstabResult, rr_each,
+        ss_each).  With plans, choose a small check_every: a step enqueued in vain runs four solves."""
+        return _pbicgstab("smvp_csr_pbicgstab", self._h, b, x, first, second, m, x0, max_steps, tol, check_every, stream)
+
     def spmm(self, X, Y, stream=None):
         """Y = A X for k vectors at once (smvp_csr_spmm): X (cols x k) and Y (rows x k) are float64 CUDA tensors with
         stride(1) == 1, ldx = X.stride(0), ldy = Y.stride(0).  Every column of Y is the serial loop's bits.  Asynchronous on
@@ -1056,6 +1089,12 @@ class TjdsMatrix:
         ref-quirks): operands and result as CsrMatrix.bicgstab.  Afterwards the handle's permuted operand is the last vector
         multiplied: call set_x before the next spmv."""
         return _bicgstab("smvp_tjds_bicgstab", self._h, b, x, x0, max_steps, tol, check_every, stream)
+
+    def pbicgstab(self, b, x, first=None, second=None, m=None, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Right-preconditioned BiCGSTAB for A x = b on this handle's product in its current mode (smvp_tjds_pbicgstab, K18;
+        ROW_GATHER or TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.pbicgstab.  The plans belong to CsrMatrix
+        objects; Jacobi (m = 1 / diagonal() alone) needs none."""
+        return _pbicgstab("smvp_tjds_pbicgstab", self._h, b, x, first, second, m, x0, max_steps, tol, check_every, stream)
 
     def spmv_transposed(self, x, y, stream=None):
         """y = A^T x from the TJDS arrays themselves (smvp_tjds_spmv_transposed, K8): x of `rows`, y of `cols` float64 CUDA
