@@ -1,39 +1,42 @@
-// smvp_bicgstab.hip -- K13: BiCGSTAB on a handle's own product (smvp_csr_bicgstab, smvp_tjds_bicgstab): A x = b for a general square
-// matrix, to the bits include/smvp_amd.h defines.  New: the reference only ever multiplies.  The dot, its folds, the grid rule and
-// the workspace holder are K12's (smvp_cg_common.h).
+// smvp_bicgstab.hip -- BiCGSTAB on a handle's own product, A x = b for a general square matrix, to the bits include/smvp_amd.h
+// defines: K13 without a preconditioner (smvp_csr_bicgstab, smvp_tjds_bicgstab) and K18, right-preconditioned with K16's
+// M = T1 diag(m)^-1 T2, each of the three parts optional (smvp_csr_pbicgstab, smvp_tjds_pbicgstab).  New: the reference only ever
+// multiplies.  The dot, its folds, the grid rule, the workspace holder, krylov_apply and the launch discipline are
+// smvp_cg_common.h's; the solves are K15's kernels, enqueued through smvp::trsv_enqueue.
 //
-// A step k has x_{k-1} in the caller's d_x, r_{k-1}, p_{k-1}, the shadow residual rhat = r_0 and rho_{k-1} = dot(rhat, r_{k-1}) in the
-// status block.  Its two products are the handle's own launches, whatever its plan: v = A p_{k-1} before the first launch below,
-// t = A s between the second and the third.  Beside them it is five launches of the dot's grid, eighteen vector passes:
+// One set of kernels and one host loop.  A step k has x_{k-1} in the caller's d_x, r_{k-1}, p_{k-1}, the shadow residual rhat = r_0
+// and rho_{k-1} = dot(rhat, r_{k-1}) in the status block.  K18: phat = M^-1 p_{k-1} comes first, then v = A phat (the handle's own
+// launch, whatever its plan); shat = M^-1 s and t = A shat sit between the second and the third launch below.  K13 is the same
+// loop with no M^-1: v = A p, t = A s, five vectors and not seven, and the plain bi_full.  Beside the two products and the solves'
+// own launches a step is five launches of the dot's grid; K13: eighteen vector passes, K18: nineteen.
 //
 //   bi_sigma_parts  the partials of sigma = dot(rhat, v)                                             (rhat, v read: 2 passes)
-//   bi_half         every workgroup folds those partials itself and so holds the same sigma and alpha = rho_{k-1} / sigma; rule A.
-//                   s = r - alpha v, written over r, and the partials of ss = dot(s, s) in the same pass
-//                                                                                               (v, r read, r written: 3 passes)
+//   bi_half         every workgroup folds those partials itself: sigma, alpha = rho_{k-1} / sigma, rule A.  s = r - alpha v over r
+//                   with the partials of ss = dot(s, s)                                     (v, r read, r written: 3 passes)
 //   bi_t_parts      the partials of ts = dot(t, s) and tt = dot(t, t) in one pass: two accumulators per lane, each in the dot's
-//                   order                                                                                (t, s read: 2 passes)
-//   bi_full         every workgroup folds ss, ts and tt and evaluates rules H and T.  x = (x + alpha p) + omega s and
-//                   r = s - omega t with the partials of rr = dot(r, r) and rho = dot(rhat, r) in the same pass
-//                   (x, p, s, t, rhat read, x, r written: 7 passes); where rule H converges or rule T breaks down, only
-//                   x = x + alpha p, the half update
+//                   order                                                                            (t, s read: 2 passes)
+//   bi_full         every workgroup folds ss, ts and tt and evaluates rules H and T.  x = (x + alpha phat) + omega shat and
+//                   r = s - omega t with the partials of rr = dot(r, r) and rho = dot(rhat, r)
+//                   (x, phat, shat, s, t, rhat read, x, r written: 8 passes; bi_full<false>, K13's, reads p for phat and s once for
+//                   both of its uses: 7 passes); where rule H converges or rule T breaks down, only x = x + alpha phat
 //   bi_direction    every workgroup folds rr and rho and evaluates rule B; p = r + beta (p - omega v) unless the run stops here
 //                   (r, p, v read, p written: 4 passes).  Workgroup 0 writes the step's status block and the history elements.
 //
-// No launch reads a word that another lane of the same launch writes, and every hand-off between workgroups is a launch boundary:
-// every dot has partials of its own, written by one launch and folded by later ones; sigma (from bi_half's workgroup 0) and ss, ts,
-// tt (from bi_full's) reach the later launches of the step through words of their own, written by plain stores; the status block is
-// ping-ponged by step parity because bi_direction reads step k - 1's while its workgroup 0 writes step k's.  No atomics.  The
-// device evaluates the rules at every step.  Rule A is known to every launch from bi_half on, rules H and T from bi_full on; once a
-// rule has fired, every later launch sees it (in the step's words, then as `stopped` in the status block) and writes nothing to
-// x, r, p or the histories -- the products enqueued in vain write the workspace's v and t only.  The host reads the block at looked
-// steps only, and only to leave the loop.  Every operation on an element is one rounded IEEE operation (-ffp-contract=off).
+// Without a `first` the multiplication by m needs no launch of its own: the kernel that produces y writes m_i * y_i beside it in the
+// same pass (Scaled: bi_start and bi_direction write phat, bi_half writes shat: Jacobi is five launches a step and 23 passes, not
+// seven and 25), and `second` solves in place on that.  With a `first` it is krylov_scale between the solves.  With neither a `first`
+// nor an m, `second` solves straight from p or s.  The bits are the same either way.
+//
+// sigma (from bi_half's workgroup 0) and ss, ts, tt (from bi_full's) reach the later launches of the step through words of their own.
+// Rule A is known to every launch from bi_half on, rules H and T from bi_full on; once a rule has fired, every later launch sees it
+// (in the step's words, then as `stopped` in the status block) and writes nothing to x, r, p, phat, shat or the histories; the
+// products, the solves and krylov_scale enqueued in vain write the workspace's v, t, phat and shat only.
 #include "smvp_cg_common.h"
 #include "smvp_engine.h"
 #include "smvp_kernels.h"
 
 #include <cmath>
 #include <cstring>
-#include <limits>
 
 namespace smvp {
 
@@ -49,7 +52,7 @@ struct BiStatus {
     int reason;   // SMVP_BICGSTAB_*
     int steps;    // the step the run stopped in
     int full;     // complete updates of x
-    int half;     // d_x holds the alpha * p half update on top of them
+    int half;     // d_x holds the alpha * phat half update on top of them
     int nss;      // elements of the ss history: the steps that reached rule H
 };
 
@@ -58,15 +61,7 @@ enum { kBiSigma = 0, kBiSs = 1, kBiTs = 2, kBiTt = 3, kBiWords = 4 };
 
 __device__ inline bool bi_rule_a(double sigma) { return !cg_finite(sigma) || sigma == 0.0; }
 
-__global__ __launch_bounds__(kCgBlock) void bi_dot_parts(const double *__restrict__ a, const double *__restrict__ b, int n,
-                                                         double *__restrict__ parts)
-{
-    const double c = cg_fold256(cg_lane_dot(a, b, n));
-    if (threadIdx.x == 0)
-        parts[blockIdx.x] = c;
-}
-
-// step k's sigma: as bi_dot_parts, and nothing once the run has stopped
+// step k's sigma: as krylov_dot_parts, and nothing once the run has stopped
 __global__ __launch_bounds__(kCgBlock) void bi_sigma_parts(const double *__restrict__ rhat, const double *__restrict__ v, int n,
                                                            const BiStatus *__restrict__ prev, double *__restrict__ parts)
 {
@@ -77,9 +72,12 @@ __global__ __launch_bounds__(kCgBlock) void bi_sigma_parts(const double *__restr
         parts[blockIdx.x] = c;
 }
 
-// r_0 = b - q (q = A x_0), or b itself without a q; rhat = p_0 = r_0; the partials of rr_0 = dot(r_0, r_0)
+// r_0 = b - q (q = A x_0), or b itself without a q; rhat = p_0 = r_0; the partials of rr_0 = dot(r_0, r_0).  Scaled: phat_i =
+// m_i * p_i in the same pass.
+template <bool Scaled>
 __global__ __launch_bounds__(kCgBlock) void bi_start(const double *__restrict__ b, const double *__restrict__ q, double *__restrict__ r,
-                                                     double *__restrict__ rhat, double *__restrict__ p, int n, double *__restrict__ parts)
+                                                     double *__restrict__ rhat, double *__restrict__ p, const double *__restrict__ m,
+                                                     double *__restrict__ phat, int n, double *__restrict__ parts)
 {
     const long long stride = (long long)gridDim.x * kCgBlock;
     double c = 0.0;
@@ -88,6 +86,8 @@ __global__ __launch_bounds__(kCgBlock) void bi_start(const double *__restrict__ 
         r[i] = v;
         rhat[i] = v;
         p[i] = v;
+        if (Scaled)
+            phat[i] = m[i] * v;
         const double t = v * v;
         c = c + t;
     }
@@ -121,9 +121,12 @@ __global__ __launch_bounds__(kCgBlock) void bi_start_finish(const double *__rest
 }
 
 // step k: prev = the status of step k - 1, parts_sigma = the partials of dot(rhat, v).  s = r - alpha v over r, the partials of ss.
-__global__ __launch_bounds__(kCgBlock) void bi_half(const double *__restrict__ v, double *__restrict__ r, int n, int nparts,
-                                                    const double *__restrict__ parts_sigma, const BiStatus *__restrict__ prev,
-                                                    double *__restrict__ words, double *__restrict__ parts_ss)
+// Scaled: shat_i = m_i * s_i in the same pass.
+template <bool Scaled>
+__global__ __launch_bounds__(kCgBlock) void bi_half(const double *__restrict__ v, double *__restrict__ r, const double *__restrict__ m,
+                                                    double *__restrict__ shat, int n, int nparts, const double *__restrict__ parts_sigma,
+                                                    const BiStatus *__restrict__ prev, double *__restrict__ words,
+                                                    double *__restrict__ parts_ss)
 {
     if (prev->stopped)
         return;
@@ -137,16 +140,20 @@ __global__ __launch_bounds__(kCgBlock) void bi_half(const double *__restrict__ v
     long long i = (long long)blockIdx.x * kCgBlock + threadIdx.x;
     double c = 0.0;
     for (; i + (kCgTrips - 1) * stride < n; i += kCgTrips * stride) {
-        double s[kCgTrips], av[kCgTrips];
+        double s[kCgTrips], av[kCgTrips], mv[kCgTrips];
 #pragma unroll
         for (int u = 0; u < kCgTrips; ++u) {
             av[u] = alpha * v[i + u * stride];  // rounded, then the difference is rounded
             s[u] = r[i + u * stride];
+            if (Scaled)
+                mv[u] = m[i + u * stride];
         }
 #pragma unroll
         for (int u = 0; u < kCgTrips; ++u) {
             s[u] = s[u] - av[u];
             r[i + u * stride] = s[u];
+            if (Scaled)
+                shat[i + u * stride] = mv[u] * s[u];
             const double t = s[u] * s[u];
             c = c + t;
         }
@@ -155,6 +162,8 @@ __global__ __launch_bounds__(kCgBlock) void bi_half(const double *__restrict__ v
         const double av = alpha * v[i];
         const double s = r[i] - av;
         r[i] = s;
+        if (Scaled)
+            shat[i] = m[i] * s;
         const double t = s * s;
         c = c + t;
     }
@@ -201,12 +210,16 @@ __global__ __launch_bounds__(kCgBlock) void bi_t_parts(const double *__restrict_
     }
 }
 
-// step k: rules H and T; x = (x + alpha p) + omega s, r = s - omega t (over s) with the partials of rr and rho, or the half update
-__global__ __launch_bounds__(kCgBlock) void bi_full(double *__restrict__ x, const double *__restrict__ p, double *__restrict__ r,
-                                                    const double *__restrict__ t, const double *__restrict__ rhat, int n, int nparts,
-                                                    const double *__restrict__ parts_ss, const double *__restrict__ parts_ts,
-                                                    const double *__restrict__ parts_tt, const BiStatus *__restrict__ prev,
-                                                    double *__restrict__ words, double *__restrict__ parts_rr, double *__restrict__ parts_rho)
+// step k: rules H and T; x = (x + alpha phat) + omega shat, r = s - omega t (over s) with the partials of rr and rho, or the half
+// update x = x + alpha phat.  Hat = false (K13, no M^-1): phat is p itself, s is read once from r for both of its uses, and shat
+// is not touched.
+template <bool Hat>
+__global__ __launch_bounds__(kCgBlock) void bi_full(double *__restrict__ x, const double *__restrict__ phat, const double *__restrict__ shat,
+                                                    double *__restrict__ r, const double *__restrict__ t, const double *__restrict__ rhat,
+                                                    int n, int nparts, const double *__restrict__ parts_ss,
+                                                    const double *__restrict__ parts_ts, const double *__restrict__ parts_tt,
+                                                    const BiStatus *__restrict__ prev, double *__restrict__ words,
+                                                    double *__restrict__ parts_rr, double *__restrict__ parts_rho)
 {
     if (prev->stopped)
         return;
@@ -238,25 +251,26 @@ __global__ __launch_bounds__(kCgBlock) void bi_full(double *__restrict__ x, cons
     }
     if (half) {
         for (; i < n; i += stride) {
-            const double ap = alpha * p[i];
+            const double ap = alpha * phat[i];
             x[i] = x[i] + ap;
         }
         return;
     }
     double crr = 0.0, crho = 0.0;
     for (; i + (kCgTrips - 1) * stride < n; i += kCgTrips * stride) {
-        double xv[kCgTrips], pv[kCgTrips], sv[kCgTrips], tv[kCgTrips], hv[kCgTrips];
+        double xv[kCgTrips], pv[kCgTrips], qv[kCgTrips], sv[kCgTrips], tv[kCgTrips], hv[kCgTrips];
 #pragma unroll
         for (int u = 0; u < kCgTrips; ++u) {
             xv[u] = x[i + u * stride];
-            pv[u] = p[i + u * stride];
+            pv[u] = phat[i + u * stride];
             sv[u] = r[i + u * stride];
+            qv[u] = Hat ? shat[i + u * stride] : sv[u];
             tv[u] = t[i + u * stride];
             hv[u] = rhat[i + u * stride];
         }
 #pragma unroll
         for (int u = 0; u < kCgTrips; ++u) {
-            const double ap = alpha * pv[u], os = omega * sv[u], ot = omega * tv[u];
+            const double ap = alpha * pv[u], os = omega * qv[u], ot = omega * tv[u];
             const double xh = xv[u] + ap;
             x[i + u * stride] = xh + os;
             const double rv = sv[u] - ot;
@@ -268,7 +282,7 @@ __global__ __launch_bounds__(kCgBlock) void bi_full(double *__restrict__ x, cons
     }
     for (; i < n; i += stride) {
         const double sv = r[i];
-        const double ap = alpha * p[i], os = omega * sv, ot = omega * t[i];
+        const double ap = alpha * phat[i], os = omega * (Hat ? shat[i] : sv), ot = omega * t[i];
         const double xh = x[i] + ap;
         x[i] = xh + os;
         const double rv = sv - ot;
@@ -285,13 +299,15 @@ __global__ __launch_bounds__(kCgBlock) void bi_full(double *__restrict__ x, cons
     }
 }
 
-// step k: the rules once more, in their order, for the status block; rule B; p = r + beta (p - omega v) unless the run stops here.
-// Workgroup 0 writes status block k and the histories.
+// step k: the rules once more, in their order, for the status block; rule B; p = r + beta (p - omega v) unless the run stops here
+// (Scaled: phat_i = m_i * p_i in the same pass).  Workgroup 0 writes status block k and the histories.
+template <bool Scaled>
 __global__ __launch_bounds__(kCgBlock) void bi_direction(double *__restrict__ p, const double *__restrict__ r, const double *__restrict__ v,
-                                                         int n, int nparts, const double *__restrict__ parts_rr,
-                                                         const double *__restrict__ parts_rho, const double *__restrict__ words,
-                                                         const BiStatus *__restrict__ prev, BiStatus *__restrict__ cur, int step, int max_steps,
-                                                         double *__restrict__ hist_rr, double *__restrict__ hist_ss)
+                                                         const double *__restrict__ m, double *__restrict__ phat, int n, int nparts,
+                                                         const double *__restrict__ parts_rr, const double *__restrict__ parts_rho,
+                                                         const double *__restrict__ words, const BiStatus *__restrict__ prev,
+                                                         BiStatus *__restrict__ cur, int step, int max_steps, double *__restrict__ hist_rr,
+                                                         double *__restrict__ hist_ss)
 {
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;
     BiStatus s = *prev;
@@ -370,61 +386,69 @@ __global__ __launch_bounds__(kCgBlock) void bi_direction(double *__restrict__ p,
     const long long stride = (long long)gridDim.x * kCgBlock;
     long long i = (long long)blockIdx.x * kCgBlock + threadIdx.x;
     for (; i + (kCgTrips - 1) * stride < n; i += kCgTrips * stride) {
-        double pv[kCgTrips], rv[kCgTrips], ov[kCgTrips];
+        double pv[kCgTrips], rv[kCgTrips], ov[kCgTrips], mv[kCgTrips];
 #pragma unroll
         for (int u = 0; u < kCgTrips; ++u) {
             ov[u] = omega * v[i + u * stride];
             pv[u] = p[i + u * stride];
             rv[u] = r[i + u * stride];
+            if (Scaled)
+                mv[u] = m[i + u * stride];
         }
 #pragma unroll
         for (int u = 0; u < kCgTrips; ++u) {
             const double d = pv[u] - ov[u];
             const double bd = beta * d;
-            p[i + u * stride] = rv[u] + bd;
+            const double pn = rv[u] + bd;
+            p[i + u * stride] = pn;
+            if (Scaled)
+                phat[i + u * stride] = mv[u] * pn;
         }
     }
     for (; i < n; i += stride) {
         const double ov = omega * v[i];
         const double d = p[i] - ov;
         const double bd = beta * d;
-        p[i] = r[i] + bd;
+        const double pn = r[i] + bd;
+        p[i] = pn;
+        if (Scaled)
+            phat[i] = m[i] * pn;
     }
 }
 
-using BiWork = KrylovWork<BiStatus>;  // r, p, v, t, rhat; the partials of six dots, the step's words, the histories
+using BiWork = KrylovWork<BiStatus>;  // r, p, v, t, rhat (K18: and phat, shat); the partials of six dots, the step's words, the histories
 
 }  // namespace
 
 int bicgstab_check_args(const char *fn, const void *h, const smvp_bicgstab_opts_t *o, const smvp_bicgstab_result_t *result, const double *d_b)
 {
-    if (!h || !o || !result || !d_b)
-        return smvp::fail(SMVP_ERR_INVALID, "%s: null %s", fn, !h ? "handle" : !o ? "opts" : !result ? "result" : "d_b");
-    if (o->struct_size != (unsigned)sizeof(smvp_bicgstab_opts_t))
-        return smvp::fail(SMVP_ERR_INVALID, "%s: smvp_bicgstab_opts_t of %u bytes, this library's has %u: initialise it with "
-                                            "smvp_bicgstab_opts_default and build against this library's header",
-                          fn, o->struct_size, (unsigned)sizeof(smvp_bicgstab_opts_t));
-    if (o->max_steps < 1 || o->check_every < 1 || !(o->tol >= 0.0) || !(o->tol <= std::numeric_limits<double>::max()))
-        return smvp::fail(SMVP_ERR_INVALID, "%s: max_steps = %d, check_every = %d, tol = %g (need max_steps >= 1, check_every >= 1, "
-                                            "tol >= 0 and finite)", fn, o->max_steps, o->check_every, o->tol);
+    return krylov_check_args(fn, "bicgstab", h, o, result, d_b);
+}
+
+int pbicgstab_check_args(const char *fn, const void *h, const smvp_bicgstab_opts_t *o, const smvp_bicgstab_result_t *result,
+                         const double *d_b, const KrylovPrecond &M)
+{
+    if (int rc = bicgstab_check_args(fn, h, o, result, d_b))
+        return rc;
+    if (!M.first && !M.d_m && !M.second)
+        return smvp::fail(SMVP_ERR_INVALID, "%s: first, d_m and second are all NULL: there is no preconditioner (smvp_csr_bicgstab / "
+                                            "smvp_tjds_bicgstab run BiCGSTAB without one)", fn);
     return SMVP_OK;
 }
 
 int bicgstab_run(const char *fn, int device, int rows, int cols, const smvp_bicgstab_opts_t *o, const double *d_b, const double *d_x0,
-                 double *d_x, smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream, const HandleProduct &product)
+                 double *d_x, const KrylovPrecond *precond, smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream,
+                 const HandleProduct &product)
 {
-    if (rows != cols)
-        return smvp::fail(SMVP_ERR_INVALID, "%s: BiCGSTAB needs a square matrix (%d x %d given)", fn, rows, cols);
+    const KrylovPrecond M = precond ? *precond : KrylovPrecond{};
+    if (int rc = krylov_check_operands(fn, "BiCGSTAB needs", device, rows, cols, M, d_b, d_x0, d_x))
+        return rc;
     const int n = rows;
-    if (n > 0 && !d_x)
-        return smvp::fail(SMVP_ERR_INVALID, "%s: null d_x", fn);
-    if (d_x0 != d_x && operands_overlap(d_x0, 1, n, d_x, 1, n, 1))
-        return smvp::fail(SMVP_ERR_INVALID, "%s: d_x0 and d_x overlap without being the same vector", fn);
-    if (operands_overlap(d_b, 1, n, d_x, 1, n, 1))
-        return smvp::fail(SMVP_ERR_INVALID, "%s: d_b and d_x overlap", fn);
     DeviceScope on(device);
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = refuse_capture(st, "BiCGSTAB allocates and synchronises, so it cannot be captured (the stream is capturing)"))
+    if (int rc = refuse_capture(st, precond ? "preconditioned BiCGSTAB allocates and synchronises, so it cannot be captured (the stream is "
+                                              "capturing)"
+                                            : "BiCGSTAB allocates and synchronises, so it cannot be captured (the stream is capturing)"))
         return rc;
     smvp_bicgstab_result_t res;
     memset(&res, 0, sizeof res);
@@ -437,64 +461,70 @@ int bicgstab_run(const char *fn, int device, int rows, int cols, const smvp_bicg
     BiWork w;
     w.stream = st;
     const int max_steps = o->max_steps, grid = cg_grid(n);
-    const size_t small_doubles = 6 * (size_t)kCgGridCap + kBiWords + 2 * (size_t)max_steps + 1;
-    const size_t pitch = ((size_t)n + 31) / 32 * 32;  // every vector on a 256-byte boundary, as vectors of their own would be
-    if (hipMalloc((void **)&w.vec, sizeof(double) * 5 * pitch) != hipSuccess ||
-        hipMalloc((void **)&w.small, sizeof(double) * small_doubles) != hipSuccess ||
-        hipMalloc((void **)&w.st, 2 * sizeof(BiStatus)) != hipSuccess || hipHostMalloc((void **)&w.seen, sizeof(BiStatus)) != hipSuccess) {
-        (void)hipGetLastError();
-        return smvp::fail(SMVP_ERR_ALLOC, "%s: cannot allocate the workspace (%d elements, %d steps)", fn, n, max_steps);
-    }
+    const size_t pitch = krylov_pitch(n);
+    if (int rc = krylov_alloc(w, fn, n, max_steps, (precond ? 7 : 5) * pitch, 6 * (size_t)kCgGridCap + kBiWords + 2 * (size_t)max_steps + 1))
+        return rc;
     double *r = w.vec, *p = r + pitch, *v = p + pitch, *t = v + pitch, *rhat = t + pitch;
+    double *phat = precond ? rhat + pitch : p, *shat = precond ? phat + pitch : r;  // K13: the products read p and s themselves
     double *parts_sigma = w.small, *parts_ss = parts_sigma + kCgGridCap, *parts_ts = parts_ss + kCgGridCap;
     double *parts_tt = parts_ts + kCgGridCap, *parts_rr = parts_tt + kCgGridCap, *parts_rho = parts_rr + kCgGridCap;
     double *words = parts_rho + kCgGridCap, *hist_rr = words + kBiWords, *hist_ss = hist_rr + max_steps + 1;
     const double tol2 = o->tol * o->tol;
     const dim3 g(grid), blk(kCgBlock);
+    const bool fused = !M.first && M.d_m;  // the kernel that writes y writes m .* y beside it
 
     // step 0: x_0 into d_x, bb, r_0 = b - A x_0 (b itself without an x_0: no product), rhat = p_0 = r_0, rr_0, the first status block
-    hipLaunchKernelGGL(bi_dot_parts, g, blk, 0, st, d_b, d_b, n, parts_sigma);
-    if (d_x0) {
-        if (d_x0 != d_x)
-            HIP_TRY(hipMemcpyAsync(d_x, d_x0, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-        if (int rc = product(d_x, v))
-            return rc;
-    } else {
-        HIP_TRY(hipMemsetAsync(d_x, 0, sizeof(double) * (size_t)n, st));
-    }
-    hipLaunchKernelGGL(bi_start, g, blk, 0, st, d_b, d_x0 ? v : nullptr, r, rhat, p, n, parts_ss);
+    hipLaunchKernelGGL(krylov_dot_parts, g, blk, 0, st, d_b, d_b, n, parts_sigma);
+    if (int rc = krylov_first_x(product, d_x0, d_x, v, n, st))
+        return rc;
+    if (fused)
+        hipLaunchKernelGGL(bi_start<true>, g, blk, 0, st, d_b, d_x0 ? v : nullptr, r, rhat, p, M.d_m, phat, n, parts_ss);
+    else
+        hipLaunchKernelGGL(bi_start<false>, g, blk, 0, st, d_b, d_x0 ? v : nullptr, r, rhat, p, nullptr, nullptr, n, parts_ss);
     hipLaunchKernelGGL(bi_start_finish, dim3(1), blk, 0, st, parts_sigma, parts_ss, grid, tol2, w.st, hist_rr);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(w.seen, w.st, sizeof(BiStatus), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    BiStatus hs = *w.seen;
+    BiStatus hs;
+    if (int rc = krylov_look(w, fn, w.st, 0, max_steps, &hs))
+        return rc;
 
     for (int k = 1; !hs.stopped; ++k) {
         const BiStatus *prev = w.st + ((k - 1) & 1);
         BiStatus *cur = w.st + (k & 1);
-        if (int rc = product(p, v))
+        if (int rc = krylov_apply(fn, M, p, phat, n, st))
+            return rc;
+        if (int rc = product(phat, v))
             return rc;
         hipLaunchKernelGGL(bi_sigma_parts, g, blk, 0, st, rhat, v, n, prev, parts_sigma);
-        hipLaunchKernelGGL(bi_half, g, blk, 0, st, v, r, n, grid, parts_sigma, prev, words, parts_ss);
-        if (int rc = product(r, t))  // r holds s
+        if (fused)
+            hipLaunchKernelGGL(bi_half<true>, g, blk, 0, st, v, r, M.d_m, shat, n, grid, parts_sigma, prev, words, parts_ss);
+        else
+            hipLaunchKernelGGL(bi_half<false>, g, blk, 0, st, v, r, nullptr, nullptr, n, grid, parts_sigma, prev, words, parts_ss);
+        if (int rc = krylov_apply(fn, M, r, shat, n, st))  // r holds s
+            return rc;
+        if (int rc = product(shat, t))
             return rc;
         hipLaunchKernelGGL(bi_t_parts, g, blk, 0, st, t, r, n, prev, words, parts_ts, parts_tt);
-        hipLaunchKernelGGL(bi_full, g, blk, 0, st, d_x, p, r, t, rhat, n, grid, parts_ss, parts_ts, parts_tt, prev, words, parts_rr, parts_rho);
-        hipLaunchKernelGGL(bi_direction, g, blk, 0, st, p, r, v, n, grid, parts_rr, parts_rho, words, prev, cur, k, max_steps, hist_rr,
-                           hist_ss);
+        if (precond)
+            hipLaunchKernelGGL(bi_full<true>, g, blk, 0, st, d_x, phat, shat, r, t, rhat, n, grid, parts_ss, parts_ts, parts_tt, prev, words,
+                               parts_rr, parts_rho);
+        else
+            hipLaunchKernelGGL(bi_full<false>, g, blk, 0, st, d_x, p, nullptr, r, t, rhat, n, grid, parts_ss, parts_ts, parts_tt, prev, words,
+                               parts_rr, parts_rho);
+        if (fused)
+            hipLaunchKernelGGL(bi_direction<true>, g, blk, 0, st, p, r, v, M.d_m, phat, n, grid, parts_rr, parts_rho, words, prev, cur, k,
+                               max_steps, hist_rr, hist_ss);
+        else
+            hipLaunchKernelGGL(bi_direction<false>, g, blk, 0, st, p, r, v, nullptr, nullptr, n, grid, parts_rr, parts_rho, words, prev, cur,
+                               k, max_steps, hist_rr, hist_ss);
         HIP_TRY(hipGetLastError());
-        if (k % o->check_every == 0 || k == max_steps) {  // a looked step: the status block, nothing else, and only to leave the loop
-            HIP_TRY(hipMemcpyAsync(w.seen, cur, sizeof(BiStatus), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            hs = *w.seen;
-            if (k == max_steps && !hs.stopped)
-                return smvp::fail(SMVP_ERR_HIP, "%s: the device did not stop at max_steps = %d", fn, max_steps);
-        }
+        if (k % o->check_every == 0 || k == max_steps)
+            if (int rc = krylov_look(w, fn, cur, k, max_steps, &hs))
+                return rc;
     }
-    if (rr_each)
-        HIP_TRY(hipMemcpy(rr_each, hist_rr, sizeof(double) * ((size_t)hs.full + 1), hipMemcpyDeviceToHost));
-    if (ss_each && hs.nss > 0)
-        HIP_TRY(hipMemcpy(ss_each, hist_ss, sizeof(double) * (size_t)hs.nss, hipMemcpyDeviceToHost));
+    if (int rc = krylov_history(rr_each, hist_rr, hs.full + 1))
+        return rc;
+    if (int rc = krylov_history(ss_each, hist_ss, hs.nss))
+        return rc;
     res.steps = hs.steps;
     res.full = hs.full;
     res.half = hs.half;

@@ -188,51 +188,40 @@ int power_check_args(const char *fn, const void *h, const smvp_power_opts_t *opt
 int power_run(const char *fn, int device, int rows, int cols, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
               smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream, const HandleProduct &product);
 
-// -------------------------------------------------------------------------------------- conjugate gradients (K12)
-// smvp_cg.hip runs the steps around the same product hook, checked and handed over by the handle files as for K11.  cg_check_args
-// makes no HIP call; cg_run checks the operands and the stream, then allocates, iterates and frees.
-int cg_check_args(const char *fn, const void *h, const smvp_cg_opts_t *opts, const smvp_cg_result_t *result, const double *d_b);
-int cg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
-           smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream, const HandleProduct &product);
-
-// ------------------------------------------------------------- conjugate gradients with a diagonal preconditioner (K14)
-// smvp_pcg.hip runs K12's steps with z = r ./ m around the same product hook, checked and handed over as for K12.  pcg_check_args
-// makes no HIP call; pcg_run checks the operands and the stream, then allocates, iterates and frees.
-int pcg_check_args(const char *fn, const void *h, const smvp_cg_opts_t *opts, const smvp_pcg_result_t *result, const double *d_b,
-                   const double *d_m);
-int pcg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
-            const double *d_m, smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each, void *stream,
-            const HandleProduct &product);
-
-// ------------------------------------------------------- conjugate gradients preconditioned by two triangular solves (K16)
-// smvp_pcg_tri.hip runs K14's steps with z = T2^-1 (m .* (T1^-1 r)) around the same product hook.  The plans are K15's
+// ------------------------------------------------------------------------------- the Krylov solvers (K12 to K14, K16, K18)
+// smvp_cg.hip and smvp_bicgstab.hip run the steps around the same product hook, checked and handed over by the handle files as for
+// K11.  The *_check_args make no HIP call; the *_run check the plans, the operands and the stream, then allocate, iterate and free.
+// A preconditioner is M = T1 diag(m)^-1 T2: z = T2^-1 (m .* (T1^-1 r)), any part may be missing.  The plans are K15's
 // (smvp_trsv.hip): trsv_enqueue is the launch loop smvp_trsv_solve itself goes through, with the operands checked and the plan's
-// device current already; trsv_rows and trsv_device say what a plan was made for.  pcg_tri_check_args makes no HIP call;
-// pcg_tri_run checks the plans, the operands and the stream, then allocates, iterates and frees.
+// device current already; trsv_rows and trsv_device say what a plan was made for.
 int trsv_rows(const smvp_trsv_t *t);
 int trsv_device(const smvp_trsv_t *t);
 int trsv_enqueue(const char *fn, smvp_trsv_t *t, const double *d_b, double *d_x, hipStream_t stream);
-int pcg_tri_check_args(const char *fn, const void *h, const smvp_cg_opts_t *opts, const smvp_pcg_result_t *result, const double *d_b,
-                       const smvp_trsv_t *first, const smvp_trsv_t *second);
-int pcg_tri_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0,
-                double *d_x, smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
-                double *rz_each, double *sigma_each, void *stream, const HandleProduct &product);
+struct KrylovPrecond {
+    smvp_trsv_t *first = nullptr;
+    const double *d_m = nullptr;
+    smvp_trsv_t *second = nullptr;
+};
 
-// ------------------------------------------------------------------------------------------------- BiCGSTAB (K13)
-// smvp_bicgstab.hip runs the steps around the same product hook, two products a step, checked and handed over as for K12.
+// conjugate gradients.  Where z = M^-1 r comes from: r itself (K12), r ./ m with M's d_m alone (K14), or a vector the two solves
+// fill, with m between them where there is one (K16).  K12 fills its own result block, which has no rz.
+enum class Precond { none, diagonal, stored };
+int cg_check_args(const char *fn, const void *h, const smvp_cg_opts_t *opts, const void *result, const double *d_b, Precond kind,
+                  const KrylovPrecond &M);
+int cg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+           Precond kind, const KrylovPrecond &M, smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each,
+           void *stream, const HandleProduct &product);
+int cg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+           smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream, const HandleProduct &product);
+
+// BiCGSTAB, two products a step.  M == nullptr: K13; else K18 with phat = M^-1 p and shat = M^-1 s, which pbicgstab_check_args
+// refuses where all three parts are NULL.
 int bicgstab_check_args(const char *fn, const void *h, const smvp_bicgstab_opts_t *opts, const smvp_bicgstab_result_t *result,
                         const double *d_b);
-int bicgstab_run(const char *fn, int device, int rows, int cols, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0,
-                 double *d_x, smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream, const HandleProduct &product);
-
-// ---------------------------------------------------------------------------------- preconditioned BiCGSTAB (K18)
-// smvp_pbicgstab.hip runs K13's steps with phat = M^-1 p and shat = M^-1 s, M = T1 diag(m)^-1 T2 as in K16 with each part optional,
-// around the same product hook and K15's trsv_enqueue.  pbicgstab_check_args is K13's plus "not all three NULL" and makes no HIP
-// call; pbicgstab_run checks the plans, the operands and the stream, then allocates, iterates and frees.
 int pbicgstab_check_args(const char *fn, const void *h, const smvp_bicgstab_opts_t *opts, const smvp_bicgstab_result_t *result,
-                         const double *d_b, const smvp_trsv_t *first, const double *d_m, const smvp_trsv_t *second);
-int pbicgstab_run(const char *fn, int device, int rows, int cols, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0,
-                  double *d_x, smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_bicgstab_result_t *result,
-                  double *rr_each, double *ss_each, void *stream, const HandleProduct &product);
+                         const double *d_b, const KrylovPrecond &M);
+int bicgstab_run(const char *fn, int device, int rows, int cols, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0,
+                 double *d_x, const KrylovPrecond *M, smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream,
+                 const HandleProduct &product);
 
 }  // namespace smvp

@@ -970,55 +970,66 @@ extern "C" int smvp_csr_spmv(smvp_csr_t *h, const double *d_x, double *d_y, void
     return smvp::csr_spmv_stamped(h, d_x, d_y, stream, nullptr);
 }
 
-// K11 on a CSR handle: the steps are smvp_power.hip's, the product is smvp_csr_spmv's on the current plan (which it leaves as it is)
+// What the solvers on a CSR handle (K11 to K14, K16, K18; the steps are smvp_power.hip's, smvp_cg.hip's and smvp_bicgstab.hip's) share: the
+// product is smvp_csr_spmv's on the current plan, which it leaves as it is, and a handle that belongs to a TJDS matrix is refused.
+static smvp::HandleProduct csr_product(smvp_csr_t *h, void *stream)
+{
+    return [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); };
+}
+
+static int refuse_tjds_flavor(const char *fn, const smvp_csr_t *h)
+{
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "%s: plain CSR handles only (this one belongs to a TJDS matrix)", fn);
+    return SMVP_OK;
+}
+
 extern "C" int smvp_csr_power_method(smvp_csr_t *h, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
                                      smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream)
 {
     if (int rc = smvp::power_check_args("smvp_csr_power_method", h, opts, result))
         return rc;
-    if (h->flavor != smvp::kFlavorCsr)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_power_method: plain CSR handles only (this one belongs to a TJDS matrix)");
+    if (int rc = refuse_tjds_flavor("smvp_csr_power_method", h))
+        return rc;
     return smvp::power_run("smvp_csr_power_method", h->device, h->rows, h->cols, opts, d_x0, d_x, result, lambda_each, residual_each, stream,
-                           [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+                           csr_product(h, stream));
 }
 
-// K12 on a CSR handle: the steps are smvp_cg.hip's, the product is smvp_csr_spmv's on the current plan (which it leaves as it is)
 extern "C" int smvp_csr_cg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                            smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream)
 {
-    if (int rc = smvp::cg_check_args("smvp_csr_cg", h, opts, result, d_b))
+    if (int rc = smvp::cg_check_args("smvp_csr_cg", h, opts, result, d_b, smvp::Precond::none, {}))
         return rc;
-    if (h->flavor != smvp::kFlavorCsr)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_cg: plain CSR handles only (this one belongs to a TJDS matrix)");
+    if (int rc = refuse_tjds_flavor("smvp_csr_cg", h))
+        return rc;
     return smvp::cg_run("smvp_csr_cg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rr_each, sigma_each, stream,
-                        [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+                        csr_product(h, stream));
 }
 
-// K14 on a CSR handle: the steps are smvp_pcg.hip's, the product is smvp_csr_spmv's on the current plan (which it leaves as it is)
 extern "C" int smvp_csr_pcg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                             const double *d_m, smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each,
                             void *stream)
 {
-    if (int rc = smvp::pcg_check_args("smvp_csr_pcg", h, opts, result, d_b, d_m))
+    const smvp::KrylovPrecond M{nullptr, d_m, nullptr};
+    if (int rc = smvp::cg_check_args("smvp_csr_pcg", h, opts, result, d_b, smvp::Precond::diagonal, M))
         return rc;
-    if (h->flavor != smvp::kFlavorCsr)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_pcg: plain CSR handles only (this one belongs to a TJDS matrix)");
-    return smvp::pcg_run("smvp_csr_pcg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, d_m, result, rr_each, rz_each, sigma_each,
-                         stream, [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+    if (int rc = refuse_tjds_flavor("smvp_csr_pcg", h))
+        return rc;
+    return smvp::cg_run("smvp_csr_pcg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, smvp::Precond::diagonal, M, result, rr_each, rz_each,
+                        sigma_each, stream, csr_product(h, stream));
 }
 
-// K16 on a CSR handle: the steps are smvp_pcg_tri.hip's, the product is smvp_csr_spmv's on the current plan (which it leaves as it
-// is), the two solves are the caller's plans'
 extern "C" int smvp_csr_pcg_tri(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                                 smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
                                 double *rz_each, double *sigma_each, void *stream)
 {
-    if (int rc = smvp::pcg_tri_check_args("smvp_csr_pcg_tri", h, opts, result, d_b, first, second))
+    const smvp::KrylovPrecond M{first, d_m, second};
+    if (int rc = smvp::cg_check_args("smvp_csr_pcg_tri", h, opts, result, d_b, smvp::Precond::stored, M))
         return rc;
-    if (h->flavor != smvp::kFlavorCsr)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_pcg_tri: plain CSR handles only (this one belongs to a TJDS matrix)");
-    return smvp::pcg_tri_run("smvp_csr_pcg_tri", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, first, d_m, second, result, rr_each,
-                             rz_each, sigma_each, stream, [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+    if (int rc = refuse_tjds_flavor("smvp_csr_pcg_tri", h))
+        return rc;
+    return smvp::cg_run("smvp_csr_pcg_tri", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, smvp::Precond::stored, M, result, rr_each, rz_each,
+                        sigma_each, stream, csr_product(h, stream));
 }
 
 // K14: the diagonal from the handle's own arrays (val is read in place: adopted values changed in place are seen).  No plan, nothing
@@ -1027,8 +1038,8 @@ extern "C" int smvp_csr_diagonal(const smvp_csr_t *h, double *d_diag, void *stre
 {
     if (!h || (h->rows > 0 && !d_diag))
         return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_diagonal: null %s", !h ? "handle" : "d_diag");
-    if (h->flavor != smvp::kFlavorCsr)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_diagonal: plain CSR handles only (this one belongs to a TJDS matrix)");
+    if (int rc = refuse_tjds_flavor("smvp_csr_diagonal", h))
+        return rc;
     DeviceScope on(h->device);
     const hipError_t e = smvp::launch_csr_diagonal(pow2_at_least(h->rows > 0 ? (double)h->nnz / h->rows : 0.0), h->d_row_ptr, h->d_col_ind,
                                                    h->d_val, d_diag, h->rows, h->cols, h->row0, (hipStream_t)stream);
@@ -1043,30 +1054,28 @@ smvp::CsrView smvp::csr_view(const smvp_csr_t *h)
     return {h->device, h->rows, h->cols, h->nnz, h->flavor, h->row0, h->d_row_ptr, h->d_col_ind, h->d_val, h->h_row_ptr.data()};
 }
 
-// K13 on a CSR handle: the steps are smvp_bicgstab.hip's, both products smvp_csr_spmv's on the current plan (which they leave as it is)
 extern "C" int smvp_csr_bicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                                  smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream)
 {
     if (int rc = smvp::bicgstab_check_args("smvp_csr_bicgstab", h, opts, result, d_b))
         return rc;
-    if (h->flavor != smvp::kFlavorCsr)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_bicgstab: plain CSR handles only (this one belongs to a TJDS matrix)");
-    return smvp::bicgstab_run("smvp_csr_bicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rr_each, ss_each, stream,
-                              [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+    if (int rc = refuse_tjds_flavor("smvp_csr_bicgstab", h))
+        return rc;
+    return smvp::bicgstab_run("smvp_csr_bicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, nullptr, result, rr_each, ss_each, stream,
+                              csr_product(h, stream));
 }
 
-// K18 on a CSR handle: the steps are smvp_pbicgstab.hip's, both products smvp_csr_spmv's on the current plan (which they leave as it
-// is), the solves are the caller's plans'
 extern "C" int smvp_csr_pbicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                                   smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_bicgstab_result_t *result,
                                   double *rr_each, double *ss_each, void *stream)
 {
-    if (int rc = smvp::pbicgstab_check_args("smvp_csr_pbicgstab", h, opts, result, d_b, first, d_m, second))
+    const smvp::KrylovPrecond M{first, d_m, second};
+    if (int rc = smvp::pbicgstab_check_args("smvp_csr_pbicgstab", h, opts, result, d_b, M))
         return rc;
-    if (h->flavor != smvp::kFlavorCsr)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_pbicgstab: plain CSR handles only (this one belongs to a TJDS matrix)");
-    return smvp::pbicgstab_run("smvp_csr_pbicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, first, d_m, second, result, rr_each,
-                               ss_each, stream, [h, stream](const double *x, double *y) { return smvp_csr_spmv(h, x, y, stream); });
+    if (int rc = refuse_tjds_flavor("smvp_csr_pbicgstab", h))
+        return rc;
+    return smvp::bicgstab_run("smvp_csr_pbicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, &M, result, rr_each, ss_each, stream,
+                              csr_product(h, stream));
 }
 
 // the owner kernel, whose launch can time itself on the device?

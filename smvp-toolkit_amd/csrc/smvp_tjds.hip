@@ -383,78 +383,72 @@ extern "C" int smvp_tjds_spmv(smvp_tjds_t *h, double *d_y, void *stream)
     return smvp::tjds_spmv_stamped(h, d_y, stream, nullptr);
 }
 
-// K11 on a TJDS handle: the steps are smvp_power.hip's, the product is smvp_tjds_set_x + smvp_tjds_spmv in the current mode -- one
-// that overwrites y and gives the same bits on every run
+// What the solvers on a TJDS handle (K11 to K14, K16, K18) share: the product is smvp_tjds_set_x + smvp_tjds_spmv in the current mode,
+// which has to be one that overwrites y and gives the same bits on every run.  The steps are smvp_power.hip's, smvp_cg.hip's and
+// smvp_bicgstab.hip's; the solves of K16 and K18 are the caller's plans' (on CSR handles of their own: a TJDS handle has no
+// triangular solve; Jacobi needs none).
+static smvp::HandleProduct tjds_product(smvp_tjds_t *h, void *stream)
+{
+    return [h, stream](const double *x, double *y) {
+        if (int rc = smvp_tjds_set_x(h, x, stream))
+            return rc;
+        return smvp_tjds_spmv(h, y, stream);
+    };
+}
+
+static int refuse_unless_overwrites_y(const char *fn, const smvp_tjds_t *h)
+{
+    if (!overwrites_y(h))
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "%s: %s", fn, h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
+                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
+    return SMVP_OK;
+}
+
 extern "C" int smvp_tjds_power_method(smvp_tjds_t *h, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
                                       smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream)
 {
     if (int rc = smvp::power_check_args("smvp_tjds_power_method", h, opts, result))
         return rc;
-    if (!overwrites_y(h))
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_power_method: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
-                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
+    if (int rc = refuse_unless_overwrites_y("smvp_tjds_power_method", h))
+        return rc;
     return smvp::power_run("smvp_tjds_power_method", h->device, h->rows, h->cols, opts, d_x0, d_x, result, lambda_each, residual_each, stream,
-                           [h, stream](const double *x, double *y) {
-                               if (int rc = smvp_tjds_set_x(h, x, stream))
-                                   return rc;
-                               return smvp_tjds_spmv(h, y, stream);
-                           });
+                           tjds_product(h, stream));
 }
 
-// K12 on a TJDS handle: the steps are smvp_cg.hip's, the product is K11's -- smvp_tjds_set_x + smvp_tjds_spmv in a mode that
-// overwrites y and gives the same bits on every run
 extern "C" int smvp_tjds_cg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                             smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream)
 {
-    if (int rc = smvp::cg_check_args("smvp_tjds_cg", h, opts, result, d_b))
+    if (int rc = smvp::cg_check_args("smvp_tjds_cg", h, opts, result, d_b, smvp::Precond::none, {}))
         return rc;
-    if (!overwrites_y(h))
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_cg: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
-                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
-    return smvp::cg_run("smvp_tjds_cg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rr_each, sigma_each, stream,
-                        [h, stream](const double *x, double *y) {
-                            if (int rc = smvp_tjds_set_x(h, x, stream))
-                                return rc;
-                            return smvp_tjds_spmv(h, y, stream);
-                        });
+    if (int rc = refuse_unless_overwrites_y("smvp_tjds_cg", h))
+        return rc;
+    return smvp::cg_run("smvp_tjds_cg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rr_each, sigma_each, stream, tjds_product(h, stream));
 }
 
-// K14 on a TJDS handle: the steps are smvp_pcg.hip's, the product is K11's -- smvp_tjds_set_x + smvp_tjds_spmv in a mode that
-// overwrites y and gives the same bits on every run
 extern "C" int smvp_tjds_pcg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                              const double *d_m, smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each,
                              void *stream)
 {
-    if (int rc = smvp::pcg_check_args("smvp_tjds_pcg", h, opts, result, d_b, d_m))
+    const smvp::KrylovPrecond M{nullptr, d_m, nullptr};
+    if (int rc = smvp::cg_check_args("smvp_tjds_pcg", h, opts, result, d_b, smvp::Precond::diagonal, M))
         return rc;
-    if (!overwrites_y(h))
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_pcg: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
-                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
-    return smvp::pcg_run("smvp_tjds_pcg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, d_m, result, rr_each, rz_each, sigma_each,
-                         stream, [h, stream](const double *x, double *y) {
-                             if (int rc = smvp_tjds_set_x(h, x, stream))
-                                 return rc;
-                             return smvp_tjds_spmv(h, y, stream);
-                         });
+    if (int rc = refuse_unless_overwrites_y("smvp_tjds_pcg", h))
+        return rc;
+    return smvp::cg_run("smvp_tjds_pcg", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, smvp::Precond::diagonal, M, result, rr_each, rz_each,
+                        sigma_each, stream, tjds_product(h, stream));
 }
 
-// K16 on a TJDS handle: the steps are smvp_pcg_tri.hip's, the product is K11's, the two solves are the caller's plans' (on CSR
-// handles of their own: a TJDS handle has no triangular solve)
 extern "C" int smvp_tjds_pcg_tri(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                                  smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,
                                  double *rz_each, double *sigma_each, void *stream)
 {
-    if (int rc = smvp::pcg_tri_check_args("smvp_tjds_pcg_tri", h, opts, result, d_b, first, second))
+    const smvp::KrylovPrecond M{first, d_m, second};
+    if (int rc = smvp::cg_check_args("smvp_tjds_pcg_tri", h, opts, result, d_b, smvp::Precond::stored, M))
         return rc;
-    if (!overwrites_y(h))
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_pcg_tri: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
-                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
-    return smvp::pcg_tri_run("smvp_tjds_pcg_tri", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, first, d_m, second, result, rr_each,
-                             rz_each, sigma_each, stream, [h, stream](const double *x, double *y) {
-                                 if (int rc = smvp_tjds_set_x(h, x, stream))
-                                     return rc;
-                                 return smvp_tjds_spmv(h, y, stream);
-                             });
+    if (int rc = refuse_unless_overwrites_y("smvp_tjds_pcg_tri", h))
+        return rc;
+    return smvp::cg_run("smvp_tjds_pcg_tri", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, smvp::Precond::stored, M, result, rr_each, rz_each,
+                        sigma_each, stream, tjds_product(h, stream));
 }
 
 // K14: the diagonal from the handle's own arrays (the true start_pos, not the ref-quirks edit of the plan; val is read in place).  No
@@ -471,41 +465,28 @@ extern "C" int smvp_tjds_diagonal(const smvp_tjds_t *h, double *d_diag, void *st
     return SMVP_OK;
 }
 
-// K13 on a TJDS handle: the steps are smvp_bicgstab.hip's, both products K11's -- smvp_tjds_set_x + smvp_tjds_spmv in a mode that
-// overwrites y and gives the same bits on every run
 extern "C" int smvp_tjds_bicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                                   smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream)
 {
     if (int rc = smvp::bicgstab_check_args("smvp_tjds_bicgstab", h, opts, result, d_b))
         return rc;
-    if (!overwrites_y(h))
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_bicgstab: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
-                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
-    return smvp::bicgstab_run("smvp_tjds_bicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rr_each, ss_each, stream,
-                              [h, stream](const double *x, double *y) {
-                                  if (int rc = smvp_tjds_set_x(h, x, stream))
-                                      return rc;
-                                  return smvp_tjds_spmv(h, y, stream);
-                              });
+    if (int rc = refuse_unless_overwrites_y("smvp_tjds_bicgstab", h))
+        return rc;
+    return smvp::bicgstab_run("smvp_tjds_bicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, nullptr, result, rr_each, ss_each, stream,
+                              tjds_product(h, stream));
 }
 
-// K18 on a TJDS handle: the steps are smvp_pbicgstab.hip's, both products K11's, the solves are the caller's plans' (on CSR handles
-// of their own: a TJDS handle has no triangular solve; Jacobi needs none)
 extern "C" int smvp_tjds_pbicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                                    smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_bicgstab_result_t *result,
                                    double *rr_each, double *ss_each, void *stream)
 {
-    if (int rc = smvp::pbicgstab_check_args("smvp_tjds_pbicgstab", h, opts, result, d_b, first, d_m, second))
+    const smvp::KrylovPrecond M{first, d_m, second};
+    if (int rc = smvp::pbicgstab_check_args("smvp_tjds_pbicgstab", h, opts, result, d_b, M))
         return rc;
-    if (!overwrites_y(h))
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_tjds_pbicgstab: %s", h->work.quirks ? "ref-quirks TJDS indexes the operand by row: it is no product "
-                          "of a changing operand" : "ATOMIC mode adds in the order the hardware takes the atomics: the steps would not be reproducible");
-    return smvp::pbicgstab_run("smvp_tjds_pbicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, first, d_m, second, result, rr_each,
-                               ss_each, stream, [h, stream](const double *x, double *y) {
-                                   if (int rc = smvp_tjds_set_x(h, x, stream))
-                                       return rc;
-                                   return smvp_tjds_spmv(h, y, stream);
-                               });
+    if (int rc = refuse_unless_overwrites_y("smvp_tjds_pbicgstab", h))
+        return rc;
+    return smvp::bicgstab_run("smvp_tjds_pbicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, &M, result, rr_each, ss_each, stream,
+                              tjds_product(h, stream));
 }
 
 // the row-gather product (which overwrites y) through the owner kernel of `rg`, on the operand of smvp_tjds_set_x

@@ -397,8 +397,8 @@ extern "C" int smvp_trsv_solve(smvp_trsv_t *t, const double *d_b, double *d_x, v
 int smvp::trsv_rows(const smvp_trsv_t *t) { return t->m.rows; }
 int smvp::trsv_device(const smvp_trsv_t *t) { return t->m.device; }
 
-// A solve's launches on `st`, for smvp_trsv_solve and for the solvers that apply a plan inside a step (K16, smvp_pcg_tri.hip): the
-// operands are checked and the plan's device is current already.
+// A solve's launches on `st`, for smvp_trsv_solve and for the solvers that apply a plan inside a step (K16 and K18, through
+// krylov_apply): the operands are checked and the plan's device is current already.
 int smvp::trsv_enqueue(const char *fn, smvp_trsv_t *t, const double *d_b, double *d_x, hipStream_t st)
 {
     const int upper = t->uplo == SMVP_TRSV_UPPER, unit = t->diag == SMVP_TRSV_DIAG_UNIT;

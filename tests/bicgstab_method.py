@@ -144,6 +144,16 @@ def nonsym_shuffled():
     return pi.Matrix(n, rows[order], cols[order], vals[order])
 
 
+def banded(n):
+    """Tridiagonal and not symmetric: 2 + (i mod 7) / 8 on the diagonal, -3/4 below, -1/4 above.  Cheap to build at any n, strictly
+    row-dominant, and its diagonal is not constant: Jacobi changes the run."""
+    i = np.arange(n)
+    rows = np.concatenate([i, i[1:], i[:-1]])
+    cols = np.concatenate([i, i[1:] - 1, i[:-1] + 1])
+    vals = np.concatenate([2.0 + (i % 7) / 8.0, np.full(n - 1, -0.75), np.full(n - 1, -0.25)])
+    return pi.Matrix(n, rows, cols, vals)
+
+
 def dense3(a):
     """A small matrix from its rows, the entries that are not zero stored."""
     a = np.array(a, dtype=np.float64)

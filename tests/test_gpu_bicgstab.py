@@ -216,6 +216,19 @@ def test_one_element_past_the_first_grid_trip(torch, fmt, a, b):
     H.close()
 
 
+@pytest.mark.parametrize("fmt,a,b", BOTH)
+def test_one_element_past_the_unrolled_bodies(torch, fmt, a, b):
+    """n = 8 * 2048 * 256 + 1: the smallest size at which the eight-deep body of the two-accumulator pass runs at all (the four-deep
+    bodies of the passes that write run twice), followed by one tail trip of lane 0 of workgroup 0."""
+    M = matrix("banded", 8 * bi.TRIP + 1)
+    rhs = bi.rhs(M.n)
+    H, product = handle(torch, M, fmt, a, b)
+    want = bi.run(product, rhs, None, 2, 0.0)
+    assert want[:4] == (2, 2, 0, bi.MAX_STEPS)
+    same(solve(torch, H, M.n, rhs, None, 2, 0.0, 2), want, "banded(%d), %s" % (M.n, fmt), rhs)
+    H.close()
+
+
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
 def test_sizes_around_a_wavefront_and_a_workgroup(torch, n):
     M = matrix("nonsym", n, 20300 + n)

@@ -124,7 +124,7 @@ def same(got, want, what, b=None):
 
 
 # ================================================================================================================== 1. the dot
-DOT_SIZES = [0, 1, 63, 64, 65, 255, 256, 257, 1003, 65537, cg.TRIP - 1, cg.TRIP, cg.TRIP + 1, 2 * cg.TRIP + 5]
+DOT_SIZES = [0, 1, 63, 64, 65, 255, 256, 257, 1003, 65537, cg.TRIP - 1, cg.TRIP, cg.TRIP + 1, 2 * cg.TRIP + 5, 8 * cg.TRIP + 1]
 
 
 def dot_operands(n):
@@ -246,6 +246,19 @@ def test_one_element_past_the_first_grid_trip(torch, fmt, a, b):
     want = cg.run(product, rhs, None, 6, 0.0)
     assert want[:3] == (6, 6, cg.MAX_STEPS)
     same(solve(torch, H, M.n, rhs, None, 6, 0.0, 4), want, "spd(%d), %s" % (M.n, fmt), rhs)
+    H.close()
+
+
+@pytest.mark.parametrize("fmt,a,b", BOTH)
+def test_one_element_past_the_unrolled_bodies(torch, fmt, a, b):
+    """n = 4 * 2048 * 256 + 1: the smallest size at which the four-deep bodies of the passes that write run at all, followed by one
+    tail trip of lane 0 of workgroup 0.  (The dot's eight-deep body is DOT_SIZES' last size.)"""
+    M = matrix("spd", 4 * cg.TRIP + 1)
+    rhs = cg.rhs(M.n)
+    H, product = handle(torch, M, fmt, a, b)
+    want = cg.run(product, rhs, None, 3, 0.0)
+    assert want[:3] == (3, 3, cg.MAX_STEPS)
+    same(solve(torch, H, M.n, rhs, None, 3, 0.0, 2), want, "spd(%d), %s" % (M.n, fmt), rhs)
     H.close()
 
 

@@ -31,6 +31,7 @@ pytestmark = pytest.mark.gpu
 
 MAX_STEPS = 80
 TOL = 1e-8
+banded = functools.lru_cache(maxsize=None)(bi.banded)    # built once and left unchanged
 ILU0_STEPS_ON_CONVDIFF = 11                                  # test_pbicgstab_host.py: the restatement's count with the host product
 
 
@@ -285,17 +286,6 @@ def test_sizes_around_a_wavefront_and_a_workgroup(torch, n):
         for x0 in (None, start_vector(n)):
             same(solve(torch, H, n, rhs, P, x0, 20, 1e-10, 5), P.run(product, rhs, x0, 20, 1e-10), "nonsym(%d), %s" % (n, fmt), rhs)
         H.close()
-
-
-@functools.lru_cache(maxsize=None)
-def banded(n):
-    """Tridiagonal and not symmetric: 2 + (i mod 7) / 8 on the diagonal, -3/4 below, -1/4 above.  Cheap to build at any n, strictly
-    row-dominant, and its diagonal is not constant: Jacobi changes the run."""
-    i = np.arange(n)
-    rows = np.concatenate([i, i[1:], i[:-1]])
-    cols = np.concatenate([i, i[1:] - 1, i[:-1] + 1])
-    vals = np.concatenate([2.0 + (i % 7) / 8.0, np.full(n - 1, -0.75), np.full(n - 1, -0.25)])
-    return pi.Matrix(n, rows, cols, vals)
 
 
 @pytest.mark.parametrize("n", [bi.TRIP + 1, 4 * bi.TRIP + 1])

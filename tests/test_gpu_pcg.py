@@ -348,6 +348,20 @@ def test_one_element_past_the_first_grid_trip(torch, fmt, a, b):
     H.close()
 
 
+@pytest.mark.parametrize("fmt,a,b", BOTH)
+def test_one_element_past_the_unrolled_bodies(torch, fmt, a, b):
+    """n = 4 * 2048 * 256 + 1: the smallest size at which the four-deep bodies of the passes that write run at all, followed by one
+    tail trip of lane 0 of workgroup 0."""
+    M = matrix("tridiagonal", 4 * cg.TRIP + 1)
+    m = jacobi("tridiagonal", 4 * cg.TRIP + 1)
+    rhs = cg.rhs(M.n)
+    H, product = handle(torch, M, fmt, a, b)
+    want = pcg.run(product, rhs, None, m, 3, 0.0)
+    assert want[:3] == (3, 3, pcg.MAX_STEPS)
+    same(solve(torch, H, M.n, rhs, m, None, 3, 0.0, 2), want, "tridiagonal(%d), %s" % (M.n, fmt), rhs)
+    H.close()
+
+
 # ================================================================================================================ 6. the stop rules
 def stop_cases():
     b5 = cg.rhs(300, 5)
