@@ -85,9 +85,11 @@ def handle(torch, M, fmt, a, b):
     return H, product
 
 
-def solve(torch, H, n, b, x0, max_steps, tol, every=10, stream=None, alias=False):
+def solve(torch, H, n, b, x0, max_steps, tol, every=10, stream=None, alias=False, before=None):
     """One call through the C ABI -> (steps, updates, reason, rr_each, sigma_each, x, rr, bb): cg_method.run's tuple, then the
-    result block's two doubles.  alias: d_x is d_x0.  Nothing is synchronised after the call: it returns when the work is done."""
+    result block's two doubles.  alias: d_x is d_x0.  Nothing is synchronised after the call: it returns when the work is done.
+    before: called in place of the leading torch.cuda.synchronize() with the call's device vectors (stream_order.solver_hook puts
+    them in flight on `stream`)."""
     buf, dx = guarded_y(torch, n)
     d0 = None
     if x0 is not None and alias:
@@ -98,7 +100,10 @@ def solve(torch, H, n, b, x0, max_steps, tol, every=10, stream=None, alias=False
     db = dev(torch, b)
     o, r = sm.cg_opts(max_steps, tol, every), sm.CgResult()
     rr, sigma = np.full(max_steps + 1, SENTINEL), np.full(max_steps, SENTINEL)
-    torch.cuda.synchronize()
+    if before is None:
+        torch.cuda.synchronize()
+    else:
+        before(x=dx, b=db, x0=d0)
     rc = getattr(sm.lib(), fn_of(H))(H._h, C.byref(o), sm._dev_ptr(db), sm._dev_ptr(d0), sm._dev_ptr(dx), C.byref(r), sm._p(rr),
                                      sm._p(sigma), sm._stream_ptr(stream))
     assert rc == sm.OK, sm.lib().smvp_last_error().decode()

@@ -49,7 +49,7 @@ def binned_paths(rows, cols, row_ptr, col_ind, val, first_row):
                 for band in (0,) + BANDS:
                     A.set_kernel(sm.CSR_KERNEL_BINNED, band)
                     assert A.get_kernel() == (sm.CSR_KERNEL_BINNED, band or 4096)
-                    yield "BINNED band %d, binned_overlap %d" % (band, overlap), (lambda dx, dy: A.spmv(dx, dy)), none, A.describe()[0]
+                    yield "BINNED band %d, binned_overlap %d" % (band, overlap), (lambda dx, dy, stream=None: A.spmv(dx, dy, stream=stream)), none, A.describe()[0]
             finally:
                 A.close()
 

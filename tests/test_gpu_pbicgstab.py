@@ -105,11 +105,13 @@ def plans_of(torch, kind, Cs):
     return Plans(*pb.jacobi(Cs))
 
 
-def solve(torch, H, n, b, P, x0, max_steps, tol, every=10, stream=None, alias=False):
+def solve(torch, H, n, b, P, x0, max_steps, tol, every=10, stream=None, alias=False, before=None):
     """One call through the C ABI -> (steps, full, half, reason, rr_each, ss_each, x, rr, bb): pbicgstab_method.run's tuple, then the
     result block's two doubles.  P: a Plans, or anything with first, second (TrsvPlans or None) and m (numpy or None).  alias: d_x is
     d_x0.  Nothing is synchronised after the call: it returns when the work is done.  ss_each's count is read off the sentinel as in
-    test_gpu_bicgstab.solve, and same() holds it to the restatement's."""
+    test_gpu_bicgstab.solve, and same() holds it to the restatement's.
+    before: called in place of the leading torch.cuda.synchronize() with the call's device vectors (stream_order.solver_hook puts
+    them in flight on `stream`)."""
     buf, dx = guarded_y(torch, n)
     d0 = None
     if x0 is not None and alias:
@@ -120,7 +122,10 @@ def solve(torch, H, n, b, P, x0, max_steps, tol, every=10, stream=None, alias=Fa
     db, dm = dev(torch, b), (dev(torch, P.m) if P.m is not None else None)
     o, r = sm.bicgstab_opts(max_steps, tol, every), sm.BicgstabResult()
     rr, ss = np.full(max_steps + 1, SENTINEL), np.full(max_steps, SENTINEL)
-    torch.cuda.synchronize()
+    if before is None:
+        torch.cuda.synchronize()
+    else:
+        before(x=dx, b=db, x0=d0, m=dm)
     rc = getattr(sm.lib(), fn_of(H))(H._h, C.byref(o), sm._dev_ptr(db), sm._dev_ptr(d0), sm._dev_ptr(dx),
                                      P.first._t if P.first is not None else None, sm._dev_ptr(dm),
                                      P.second._t if P.second is not None else None, C.byref(r), sm._p(rr), sm._p(ss),

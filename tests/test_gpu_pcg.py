@@ -213,10 +213,12 @@ def test_diagonal_refusals(torch):
 
 
 # ======================================================================================================= 2. the solver's calls
-def solve(torch, H, n, b, m, x0, max_steps, tol, every=10, stream=None, alias=False):
+def solve(torch, H, n, b, m, x0, max_steps, tol, every=10, stream=None, alias=False, before=None):
     """One call through the C ABI -> (steps, updates, reason, rr_each, rz_each, sigma_each, x, rr, rz, bb): pcg_method.run's tuple,
     then the result block's three doubles.  alias: d_x is d_x0.  Nothing is synchronised after the call: it returns when the work
-    is done."""
+    is done.
+    before: called in place of the leading torch.cuda.synchronize() with the call's device vectors (stream_order.solver_hook puts
+    them in flight on `stream`)."""
     buf, dx = guarded_y(torch, n)
     d0 = None
     if x0 is not None and alias:
@@ -227,7 +229,10 @@ def solve(torch, H, n, b, m, x0, max_steps, tol, every=10, stream=None, alias=Fa
     db, dm = dev(torch, b), dev(torch, m)
     o, r = sm.cg_opts(max_steps, tol, every), sm.PcgResult()
     rr, rz, sigma = np.full(max_steps + 1, SENTINEL), np.full(max_steps + 1, SENTINEL), np.full(max_steps, SENTINEL)
-    torch.cuda.synchronize()
+    if before is None:
+        torch.cuda.synchronize()
+    else:
+        before(x=dx, b=db, x0=d0, m=dm)
     rc = getattr(sm.lib(), fn_of(H))(H._h, C.byref(o), sm._dev_ptr(db), sm._dev_ptr(d0), sm._dev_ptr(dx), sm._dev_ptr(dm), C.byref(r),
                                      sm._p(rr), sm._p(rz), sm._p(sigma), sm._stream_ptr(stream))
     assert rc == sm.OK, sm.lib().smvp_last_error().decode()

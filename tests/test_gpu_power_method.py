@@ -87,9 +87,11 @@ def handle(torch, M, fmt, a, b):
     return H, product
 
 
-def power(torch, H, n, x0, max_steps, tol=0.0, every=1, stream=None, alias=False):
+def power(torch, H, n, x0, max_steps, tol=0.0, every=1, stream=None, alias=False, before=None):
     """One call through the C ABI -> (steps, reason, index, lambda_each, residual_each, scale, x), as power_method.run returns
-    them.  alias: d_x is d_x0.  Nothing is synchronised after the call: it returns when the work has finished."""
+    them.  alias: d_x is d_x0.  Nothing is synchronised after the call: it returns when the work has finished.
+    before: called in place of the leading torch.cuda.synchronize() with the call's device vectors (stream_order.solver_hook puts
+    them in flight on `stream`)."""
     buf, dx = guarded_y(torch, n)
     d0 = None
     if x0 is not None and alias:
@@ -99,7 +101,10 @@ def power(torch, H, n, x0, max_steps, tol=0.0, every=1, stream=None, alias=False
         d0 = dev(torch, x0)
     o, r = sm.power_opts(max_steps, tol, every), sm.PowerResult()
     lam, res = np.full(max_steps, SENTINEL), np.full(max_steps, SENTINEL)
-    torch.cuda.synchronize()
+    if before is None:
+        torch.cuda.synchronize()
+    else:
+        before(x=dx, x0=d0)
     rc = getattr(sm.lib(), fn_of(H))(H._h, C.byref(o), sm._dev_ptr(d0), sm._dev_ptr(dx), C.byref(r), sm._p(lam), sm._p(res),
                                      sm._stream_ptr(stream))
     assert rc == sm.OK, sm.lib().smvp_last_error().decode()

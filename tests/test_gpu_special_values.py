@@ -50,12 +50,12 @@ def serial_rows(name, row_ptr, ascending):
 
 def csr_paths(rows, cols, row_ptr, col_ind, val, only_serial=False, first_row=0):
     """(label, run, serial-rows mask or None for "not reproducible", kernel name) of every CSR path, one after the other; run(dx,
-    dy) enqueues one product.  first_row: the handles are row blocks (smvp_csr_create_block)."""
+    dy, stream=None) enqueues one product on `stream`.  first_row: the handles are row blocks (smvp_csr_create_block)."""
     ascending = bool(np.all((np.diff(col_ind.astype(np.int64)) > 0) | (np.diff(sv.row_of_entries(row_ptr)) > 0))) if len(col_ind) > 1 else True
 
     def path(A, label):
         name = A.describe()[0]
-        return label, (lambda dx, dy: A.spmv(dx, dy)), serial_rows(name, row_ptr, ascending), name
+        return label, (lambda dx, dy, stream=None: A.spmv(dx, dy, stream=stream)), serial_rows(name, row_ptr, ascending), name
 
     A = sm.CsrMatrix(rows, cols, row_ptr, col_ind, val, first_row=first_row)
     try:
@@ -98,10 +98,10 @@ def tjds_paths(rows, cols, row_ptr, col_ind, val):
     none = np.zeros(rows, dtype=bool)
 
     def run_of(T):
-        def run(dx, dy):
-            T.set_x(dx)
-            T.zero_y(dy)
-            T.spmv(dy)
+        def run(dx, dy, stream=None):
+            T.set_x(dx, stream=stream)
+            T.zero_y(dy, stream=stream)
+            T.spmv(dy, stream=stream)
         return run
 
     T = sm.TjdsMatrix(t)
