@@ -430,12 +430,12 @@ bool binned_suits(smvp_csr *h)
 // block-structured matrices): 10 instead of 12 bytes per entry.  Tried for 2048-entry tiles first on large matrices --
 // with the narrower stream the larger tile wins (memplus x944: 0.2965 ms against 0.3131 with 1024-entry tiles; 32-bit
 // columns: 0.319 / 0.325) -- unless the caller named the tile size.  Leaves h->vpt at the tile size that fits, or the
-// handle without offsets.
-void try_column_offsets(smvp_csr *h)
+// handle without offsets.  An error where the two arrays cannot be allocated or their build fails.
+int try_column_offsets(smvp_csr *h)
 {
     if (h->flavor != smvp::kFlavorCsr || h->kernel != SMVP_CSR_KERNEL_STREAM || h->vpt < 4 || h->nnz <= 0 ||
         smvp::option("csr_col16", 1) == 0)  // (plan option: 0 keeps the 32-bit columns)
-        return;
+        return SMVP_OK;
     std::vector<int> tiles;
     if (!h->tile_chosen && h->nnz >= 12 * 1024 * 1024)  // memplus x59 / x118 / x236 (7.4 / 14.9 / 29.8 M entries), 1024- against
         tiles.push_back(2048);                           // 2048-entry tiles: 0.0220 / 0.0364 / 0.0851 against 0.0219 / 0.0345 / 0.0787 ms
@@ -443,22 +443,27 @@ void try_column_offsets(smvp_csr *h)
     const size_t max_tiles = ((size_t)h->nnz + 1023) / 1024 + 1;
     int *col_base = nullptr;
     unsigned short *col16 = nullptr;
-    if (hipMalloc((void **)&col_base, max_tiles * sizeof(int)) == hipSuccess &&
-        hipMalloc((void **)&col16, ((size_t)h->nnz + 8) * sizeof(unsigned short)) == hipSuccess) {
-        for (int tile : tiles) {
-            int fits = 0;
-            if (smvp::build_column_offsets(h->d_col_ind, h->nnz, tile, col_base, col16, &fits, nullptr) == SMVP_OK && fits) {
-                h->vpt = tile / smvp::kStreamBlock;
-                h->tile.d_col_base = col_base;
-                h->tile.d_col16 = col16;
-                return;
-            }
+    // memory that runs out and a build that fails are the plan's failure, as with every other array of it; columns that do not fit
+    // only leave the handle without the second copy
+    int rc = SMVP_OK;
+    if (hipMalloc((void **)&col_base, max_tiles * sizeof(int)) != hipSuccess ||
+        hipMalloc((void **)&col16, ((size_t)h->nnz + 8) * sizeof(unsigned short)) != hipSuccess)
+        rc = smvp::fail(SMVP_ERR_ALLOC, "cannot allocate the 16-bit column offsets (%d entries)", h->nnz);
+    for (size_t i = 0; i < tiles.size() && rc == SMVP_OK; ++i) {
+        int fits = 0;
+        rc = smvp::build_column_offsets(h->d_col_ind, h->nnz, tiles[i], col_base, col16, &fits, nullptr);
+        if (rc == SMVP_OK && fits) {
+            h->vpt = tiles[i] / smvp::kStreamBlock;
+            h->tile.d_col_base = col_base;
+            h->tile.d_col16 = col16;
+            return SMVP_OK;
         }
     }
     (void)hipGetLastError();  // no second copy: the kernel reads col_ind itself
     for (void *p : {(void *)col16, (void *)col_base})
         if (p)
             (void)hipFree(p);
+    return rc;
 }
 
 // A handle's plain launches of the tile kernel sweep the tiles forward and backward in turn where one product's algorithmic
@@ -468,11 +473,12 @@ void try_column_offsets(smvp_csr *h)
 // alternating, x40 / x100 (75 / 187 MB) 0.8 / 0.3 % slower, x200 (374 MB) 8 % faster (profiles/sweep_direction_measured.txt).
 constexpr double kSweepAlternateMinBytes = 256.0 * 1024 * 1024;
 
-int build_tile_plan(smvp_csr *h)
+int build_tile_plan_parts(smvp_csr *h)
 {
     TilePlan &t = h->tile;
     free_tile_plan(&t);
-    try_column_offsets(h);
+    if (int rc = try_column_offsets(h))
+        return rc;
     const int tile = smvp::kStreamBlock * h->vpt;
     const long long nnz = h->nnz;
     const int ntiles = (int)std::max<long long>(1, (nnz + tile - 1) / tile);
@@ -552,6 +558,15 @@ int build_tile_plan(smvp_csr *h)
             return rc;
     }
     return SMVP_OK;
+}
+
+// A build that fails leaves the handle without a tile plan (smvp_csr_spmv then refuses it), never with the arrays built so far.
+int build_tile_plan(smvp_csr *h)
+{
+    const int rc = build_tile_plan_parts(h);
+    if (rc != SMVP_OK)
+        free_tile_plan(&h->tile);
+    return rc;
 }
 
 int pow2_at_least(double v)
@@ -668,9 +683,7 @@ static int plan_csr(smvp_csr *h, int kernel, int param, bool silent_fallback)
             free_binned_side(&h->binned);
             h->spread = -1.0;
             choose_csr_kernel(h, SMVP_CSR_KERNEL_STREAM, 0);
-            const int tile_rc = build_tile_plan(h);
-            if (tile_rc != SMVP_OK)
-                free_tile_plan(&h->tile);
+            const int tile_rc = build_tile_plan(h);  // (a failure leaves no tile plan)
             rc = silent_fallback ? tile_rc : smvp::fail(rc, "%s", why.c_str());
         }
     }
@@ -1294,8 +1307,13 @@ extern "C" int smvp_csr_create_transposed(smvp_csr_t **out, const smvp_csr_t *h,
     (void)hipFree(coo);
     coo = nullptr;
     smvp_csr_t *t = nullptr;
-    if (rc == SMVP_OK)
+    if (rc == SMVP_OK) {
         rc = csr_create_impl(&t, h->device, t_rows, t_cols, nnz, t_row_ptr, t_col_ind, t_val, SMVP_MEM_DEVICE, nullptr, smvp::kFlavorCsr);
+        if (rc == SMVP_ERR_HIP && strstr(smvp_last_error(), "out of memory")) {
+            (void)hipGetLastError();
+            rc = smvp::fail(SMVP_ERR_ALLOC, "smvp_csr_create_transposed: cannot allocate the transposed handle's plan (%d entries)", nnz);
+        }
+    }
     if (rc != SMVP_OK) {
         release();
         return rc;
