@@ -176,7 +176,7 @@ int sort_entries(Scratch &sc, const smvp_coo_t *d_coo, int rows, int cols, int n
     HIP_TRY(sc.get(&start, (size_t)n_major + 1));
     HIP_TRY(sc.get(&bad, 1));
     HIP_TRY(hipMemsetAsync(count, 0, sizeof(int) * ((size_t)n_major + 1), st));
-    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));  // needed: pack_keys only ever raises the flag
     if (nnz > 0) {
         hipLaunchKernelGGL(pack_keys, dim3(blocks_for(nnz)), dim3(256), 0, st, d_coo, nnz, rows, cols, minor_bits,
                            row_major, k0, i0, count, bad);

@@ -179,6 +179,43 @@ def spill_matrix(kind):
     return n, n, 0, row_ptr, c_all[order].astype(np.int32), rng.uniform(-1, 1, len(order))
 
 
+def csr_from_lengths(rng, lens, cols):
+    """(row_ptr, col_ind, val): lens[r] distinct ascending columns out of `cols` in row r, values uniform in (-1, 1)."""
+    rows = len(lens)
+    row_ptr = np.zeros(rows + 1, dtype=np.int32)
+    np.cumsum(lens, out=row_ptr[1:])
+    col_ind = np.concatenate([np.sort(rng.choice(cols, size=l, replace=False)) for l in lens] + [np.zeros(0, int)])
+    val = rng.uniform(-1, 1, int(row_ptr[-1]))
+    return row_ptr, col_ind.astype(np.int32), val
+
+
+def corner_structures():
+    """[(name, rows, cols, bands, row_ptr, col_ind, val, x)]: the binned plan where its bookkeeping is stressed --
+      wide  6000 x 3 000 000 = 184 column blocks (more than a workgroup stages shifts for); rows of 0 ... 1500 entries: far rows
+            longer than a wavefront's 32 (summed by a whole wavefront) and longer than the cap of 1024 (kept near), rows with only
+            far / only near entries, empty rows, duplicate and unsorted columns, a rectangular matrix;
+      tall  200 000 x 40 000: every column within a few blocks, many far rows per row block, stretches of rows without entries.
+    `bands` are the bands each is multiplied at.  One generator draws both, in this order."""
+    rng = np.random.default_rng(2024)
+    rows, cols = 6000, 3_000_000
+    lens = np.where(rng.random(rows) < 0.05, rng.integers(500, 1500, rows), rng.integers(0, 40, rows))
+    lens[:3] = (0, 1, 33)
+    row_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    col_ind = rng.integers(0, cols, int(row_ptr[-1])).astype(np.int32)
+    idx = np.arange(0, len(col_ind) - 1, 97)
+    col_ind[idx] = col_ind[idx + 1]                               # some repeats (mostly inside rows)
+    val = rng.uniform(-1, 1, len(col_ind))
+    x = rng.random(cols)
+    out = [("wide", rows, cols, (0, 5, 2_000_000), row_ptr, col_ind, val, x)]
+    rows, cols = 200_000, 40_000
+    lens = rng.integers(0, 9, rows)
+    lens[50_000:90_000] = 0
+    row_ptr, col_ind, val = csr_from_lengths(rng, lens.tolist(), cols)
+    x = rng.random(cols)
+    out.append(("tall", rows, cols, (16,), row_ptr, col_ind, val, x))
+    return out
+
+
 def assert_spill_regime(kind, rows, cols, band, row_ptr, col_ind):
     """The matrix of spill_matrix(kind) reaches its regime with at least 10 % to spare; returns binned_regime's numbers."""
     g = binned_regime(row_ptr, col_ind, cols, band)

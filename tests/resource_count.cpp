@@ -14,9 +14,22 @@
 //
 // smvp_test_fail_*(nth), for device memory, pinned memory, streams and events: the nth obtaining call of that kind from now on fails once with hipErrorOutOfMemory without reaching
 // the runtime (1 = the next one); -1 disarms.  Thread-safe: the sharded layer issues from threads.
+//
+// smvp_test_fill_allocations(mode, first, last): what a fresh allocation holds.  The library is correct only if every word it
+// allocates is written before it is read, or cleared by one of its own memsets; a fresh process usually gets cleared pages, so a
+// forgotten write shows only where the allocator hands back used memory.  Armed, every successful hipMalloc / hipHostMalloc of
+// the library is filled before the wrapper returns: mode 1 = every 32-bit word 0x00000001 (a tail of 1..3 bytes goes on with
+// that word's bytes, 01 00 00), mode 2 = every byte 0xFF, mode 0 = off (the default).  Device memory is filled by the
+// runtime's memset and the wrapper waits for it with hipDeviceSynchronize: the library works on non-blocking streams, which do
+// not wait for the null stream.  Pinned memory is filled on the host.  first / last: only the obtaining calls (device and
+// pinned memory in one sequence, refused ones counted) with these ordinals are filled, counted from 0 at the arming call;
+// last < 0 = no upper end, so 0, -1 fills all of them -- a failing scenario is narrowed to one allocation by halving the
+// window.  A fill that fails never changes what the allocation returns: it is counted, and the runtime's sticky error is read
+// off.  tests/test_gpu_fresh_memory.py.
 #include <hip/hip_runtime_api.h>
 
 #include <cstddef>
+#include <cstring>
 #include <mutex>
 #include <unordered_map>
 
@@ -33,6 +46,10 @@ struct State {
     long long fail_in[kKinds] = {};     // > 0: that many obtaining calls from now, the last of them fails; 0: disarmed
     long long foreign = 0;
     long long refused = 0;
+    int fill_mode = 0;                  // 0 off, 1 words of 0x00000001, 2 bytes of 0xFF
+    long long fill_first = 0, fill_last = -1;   // the window of ordinals that are filled; last < 0: no upper end
+    long long fill_ordinal = 0;         // device and pinned obtaining calls since the arming call
+    long long fills = 0, fill_bytes = 0, fill_failed = 0;
 };
 
 State &state() {
@@ -41,10 +58,14 @@ State &state() {
 }
 
 // true: this obtaining call is the one to refuse
-bool begin_obtain(Kind k) {
+bool begin_obtain(Kind k, int *fill = nullptr) {
     State &s = state();
     std::lock_guard<std::mutex> lock(s.mu);
     s.obtains[k]++;
+    if (fill) {                         // (the ordinal is taken here, with the refusal decided under the same lock)
+        const long long ordinal = s.fill_ordinal++;
+        *fill = ordinal >= s.fill_first && (s.fill_last < 0 || ordinal <= s.fill_last) ? s.fill_mode : 0;
+    }
     if (s.fail_in[k] > 0 && --s.fail_in[k] == 0) {
         s.refused++;
         return true;
@@ -78,6 +99,49 @@ bool begin_release(Kind k, const void *p) {
     return true;
 }
 
+void count_fill(size_t bytes, bool ok) {
+    State &s = state();
+    std::lock_guard<std::mutex> lock(s.mu);
+    if (ok) {
+        s.fills++;
+        s.fill_bytes += (long long)bytes;
+    } else {
+        s.fill_failed++;
+    }
+}
+
+const unsigned char kOneWord[4] = {1, 0, 0, 0};    // 0x00000001 as it lies in memory
+
+void fill_device(void *p, size_t bytes, int mode) {
+    if (!p || !bytes)
+        return;
+    hipError_t e;
+    if (mode == 2) {
+        e = hipMemset(p, 0xFF, bytes);
+    } else {
+        const size_t words = bytes / 4, tail = bytes % 4;
+        e = words ? hipMemsetD32((hipDeviceptr_t)p, 1, words) : hipSuccess;
+        if (e == hipSuccess && tail)
+            e = hipMemcpy((char *)p + 4 * words, kOneWord, tail, hipMemcpyHostToDevice);
+    }
+    const hipError_t w = hipDeviceSynchronize();
+    if (e != hipSuccess || w != hipSuccess)
+        (void)hipGetLastError();        // the allocation succeeded: its caller must not find this error
+    count_fill(bytes, e == hipSuccess && w == hipSuccess);
+}
+
+void fill_host(void *p, size_t bytes, int mode) {
+    if (!p || !bytes)
+        return;
+    if (mode == 2) {
+        std::memset(p, 0xFF, bytes);
+    } else {
+        for (size_t i = 0; i < bytes; i++)
+            ((unsigned char *)p)[i] = kOneWord[i % 4];
+    }
+    count_fill(bytes, true);
+}
+
 int arm(Kind k, int nth) {
     State &s = state();
     std::lock_guard<std::mutex> lock(s.mu);
@@ -108,14 +172,18 @@ hipError_t __real_hipGraphExecDestroy(hipGraphExec_t);
 #define SMVP_TEST_API __attribute__((visibility("default")))
 
 hipError_t __wrap_hipMalloc(void **ptr, size_t size) {
-    if (begin_obtain(kDevice)) {
+    int fill = 0;
+    if (begin_obtain(kDevice, &fill)) {
         if (ptr)
             *ptr = nullptr;             // as the runtime leaves it when memory runs out
         return hipErrorOutOfMemory;
     }
     const hipError_t e = __real_hipMalloc(ptr, size);
-    if (e == hipSuccess && ptr)
+    if (e == hipSuccess && ptr) {
         record(kDevice, *ptr, size);
+        if (fill)
+            fill_device(*ptr, size, fill);
+    }
     return e;
 }
 
@@ -124,14 +192,18 @@ hipError_t __wrap_hipFree(void *ptr) {
 }
 
 hipError_t __wrap_hipHostMalloc(void **ptr, size_t size, unsigned int flags) {
-    if (begin_obtain(kPinned)) {
+    int fill = 0;
+    if (begin_obtain(kPinned, &fill)) {
         if (ptr)
             *ptr = nullptr;
         return hipErrorOutOfMemory;
     }
     const hipError_t e = __real_hipHostMalloc(ptr, size, flags);
-    if (e == hipSuccess && ptr)
+    if (e == hipSuccess && ptr) {
         record(kPinned, *ptr, size);
+        if (fill)
+            fill_host(*ptr, size, fill);
+    }
     return e;
 }
 
@@ -231,5 +303,41 @@ SMVP_TEST_API int smvp_test_fail_device_alloc(int nth) { return arm(kDevice, nth
 SMVP_TEST_API int smvp_test_fail_host_alloc(int nth) { return arm(kPinned, nth); }
 SMVP_TEST_API int smvp_test_fail_stream_create(int nth) { return arm(kStream, nth); }
 SMVP_TEST_API int smvp_test_fail_event_create(int nth) { return arm(kEvent, nth); }
+
+// mode 0 / 1 / 2 as at the head of this file; the ordinals start again at 0.  Returns 0, or -1 for a mode it does not know
+// (nothing changes then).
+SMVP_TEST_API int smvp_test_fill_allocations(int mode, long long first, long long last) {
+    if (mode < 0 || mode > 2)
+        return -1;
+    State &s = state();
+    std::lock_guard<std::mutex> lock(s.mu);
+    s.fill_mode = mode;
+    s.fill_first = first;
+    s.fill_last = last;
+    s.fill_ordinal = 0;
+    return 0;
+}
+
+// out[0..2] = fills done, bytes filled, fills failed, since the process began
+SMVP_TEST_API void smvp_test_fill_stats(long long out[3]) {
+    State &s = state();
+    std::lock_guard<std::mutex> lock(s.mu);
+    out[0] = s.fills;
+    out[1] = s.fill_bytes;
+    out[2] = s.fill_failed;
+}
+
+// What an allocation of `bytes` holds when the library gets it: allocates through the wrapper, copies the content to host_out
+// (room for `bytes`), frees through the wrapper.  Returns the first HIP error met, 0 = none.
+SMVP_TEST_API int smvp_test_probe_fill(size_t bytes, unsigned char *host_out) {
+    void *p = nullptr;
+    hipError_t e = __wrap_hipMalloc(&p, bytes);
+    if (e != hipSuccess)
+        return (int)e;
+    if (p && bytes && host_out)
+        e = hipMemcpy(host_out, p, bytes, hipMemcpyDeviceToHost);
+    const hipError_t f = __wrap_hipFree(p);
+    return (int)(e != hipSuccess ? e : f);
+}
 
 }   // extern "C"

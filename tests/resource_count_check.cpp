@@ -1,11 +1,14 @@
 // Stand-alone check of tests/resource_count.cpp's bookkeeping, CPU only: the __real_* functions are fakes over malloc, the
-// wrappers are called by name.  Built by `make resource-check` with -fsanitize=address,undefined and run as its own process
-// by tests/test_resource_count_host.py.  Exit status 0 and "resource_count_check ok" = pass.
+// wrappers are called by name; the memset, copy and synchronise calls the fill switch makes are fakes too, which write the
+// malloc block (of exactly the size asked for, so a fill one byte too long is AddressSanitizer's to find).  Built by
+// `make resource-check` with -fsanitize=address,undefined and run as its own process by tests/test_resource_count_host.py.
+// Exit status 0 and "resource_count_check ok" = pass.
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <thread>
 #include <vector>
 
@@ -29,6 +32,9 @@ int smvp_test_fail_device_alloc(int);
 int smvp_test_fail_host_alloc(int);
 int smvp_test_fail_stream_create(int);
 int smvp_test_fail_event_create(int);
+int smvp_test_fill_allocations(int, long long, long long);
+void smvp_test_fill_stats(long long[3]);
+int smvp_test_probe_fill(size_t, unsigned char *);
 
 // ---- the fake runtime: every object is a malloc block; calls into it are counted
 static std::atomic<long long> g_real_calls{0};
@@ -63,6 +69,46 @@ hipError_t __real_hipStreamEndCapture(hipStream_t, hipGraph_t *g) { return fake_
 hipError_t __real_hipGraphDestroy(hipGraph_t g) { return fake_delete(g); }
 hipError_t __real_hipGraphInstantiate(hipGraphExec_t *x, hipGraph_t, hipGraphNode_t *, char *, size_t) { return fake_new((void **)x, 8); }
 hipError_t __real_hipGraphExecDestroy(hipGraphExec_t x) { return fake_delete(x); }
+
+// ---- what the fill calls directly (it wraps none of these): "device memory" is the malloc block, a memset is pending until
+// the next synchronise, and g_fail_memsets > 0 makes that many memsets fail and leave a sticky error behind
+static std::atomic<long long> g_memsets{0}, g_syncs{0}, g_pending{0}, g_sticky{0}, g_fail_memsets{0};
+static bool memset_fails() {
+    if (g_fail_memsets.load() > 0 && g_fail_memsets.fetch_sub(1) > 0) {
+        g_sticky = 1;
+        return true;
+    }
+    return false;
+}
+hipError_t hipMemset(void *p, int value, size_t n) {
+    g_memsets++;
+    if (memset_fails())
+        return hipErrorInvalidValue;
+    std::memset(p, value, n);
+    g_pending++;
+    return hipSuccess;
+}
+hipError_t hipMemsetD32(hipDeviceptr_t p, int value, size_t count) {
+    g_memsets++;
+    if (memset_fails())
+        return hipErrorInvalidValue;
+    for (size_t i = 0; i < count; i++)
+        std::memcpy((char *)p + 4 * i, &value, 4);
+    g_pending++;
+    return hipSuccess;
+}
+hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind) {
+    std::memcpy(dst, src, n);
+    return hipSuccess;
+}
+hipError_t hipDeviceSynchronize(void) {
+    g_syncs++;
+    g_pending = 0;
+    return hipSuccess;
+}
+hipError_t hipGetLastError(void) {
+    return g_sticky.exchange(0) ? hipErrorInvalidValue : hipSuccess;
+}
 }
 
 static int g_failed = 0;
@@ -233,12 +279,194 @@ static void threads() {
     CHECK(b.v[FOREIGN] == a.v[FOREIGN]);
 }
 
+struct Fills {
+    long long v[3];
+    long long done() const { return v[0]; }
+    long long bytes() const { return v[1]; }
+    long long failed() const { return v[2]; }
+};
+static Fills fills() {
+    Fills f;
+    smvp_test_fill_stats(f.v);
+    return f;
+}
+
+// every byte of p[0..n) is what `mode` puts there (mode 0: the 0xAB the caller wrote into it)
+static bool holds(const unsigned char *p, size_t n, int mode) {
+    static const unsigned char one[4] = {1, 0, 0, 0};
+    for (size_t i = 0; i < n; i++)
+        if (p[i] != (mode == 2 ? 0xFF : mode == 1 ? one[i % 4] : 0xAB))
+            return false;
+    return true;
+}
+
+static void fill_off_by_default() {
+    const Fills a = fills();
+    const long long sets = g_memsets.load(), syncs = g_syncs.load();
+    void *p = nullptr, *h = nullptr;
+    CHECK(__wrap_hipMalloc(&p, 64) == hipSuccess && __wrap_hipHostMalloc(&h, 64, 0) == hipSuccess);
+    unsigned char out[5] = {};
+    CHECK(smvp_test_probe_fill(5, out) == 0);
+    const Fills b = fills();
+    CHECK(b.done() == a.done() && b.bytes() == a.bytes() && b.failed() == a.failed());
+    CHECK(g_memsets.load() == sets && g_syncs.load() == syncs);
+    CHECK(__wrap_hipFree(p) == hipSuccess && __wrap_hipHostFree(h) == hipSuccess);
+    CHECK(smvp_test_fill_allocations(3, 0, -1) == -1 && smvp_test_fill_allocations(-1, 0, -1) == -1);      // unknown modes change nothing
+    CHECK(smvp_test_probe_fill(5, out) == 0 && fills().done() == a.done());
+}
+
+// the malloc blocks have exactly the size asked for: a fill one byte too long is AddressSanitizer's to find, one too short is holds()'s
+static void fill_coverage() {
+    const size_t sizes[] = {0, 1, 3, 4, 5, 4096 + 3};
+    for (int mode = 1; mode <= 2; mode++) {
+        CHECK(smvp_test_fill_allocations(mode, 0, -1) == 0);
+        for (size_t n : sizes) {
+            const Fills a = fills();
+            const long long syncs = g_syncs.load();
+            void *p = (void *)&a, *h = nullptr;
+            CHECK(__wrap_hipMalloc(&p, n) == hipSuccess && (n == 0) == (p == nullptr));
+            CHECK(g_pending.load() == 0);                       // waited for before the wrapper returned
+            CHECK(n == 0 || g_syncs.load() == syncs + 1);
+            CHECK(holds((const unsigned char *)p, n, mode));
+            CHECK(__wrap_hipHostMalloc(&h, n, 0) == hipSuccess && h);
+            CHECK(holds((const unsigned char *)h, n, mode));
+            const Fills b = fills();
+            CHECK(b.done() == a.done() + (n ? 2 : 0) && b.bytes() == a.bytes() + 2 * (long long)n && b.failed() == a.failed());
+            CHECK(__wrap_hipFree(p) == hipSuccess && __wrap_hipHostFree(h) == hipSuccess);
+            std::vector<unsigned char> out(n + 1, 0x5C);
+            CHECK(smvp_test_probe_fill(n, out.data()) == 0 && holds(out.data(), n, mode) && out[n] == 0x5C);
+        }
+    }
+    CHECK(smvp_test_fill_allocations(0, 0, -1) == 0);
+    const Fills a = fills();
+    unsigned char out[8];
+    std::memset(out, 0xAB, sizeof out);
+    void *p = nullptr;
+    CHECK(__wrap_hipMalloc(&p, 8) == hipSuccess && fills().done() == a.done());     // off again
+    CHECK(__wrap_hipFree(p) == hipSuccess);
+}
+
+static void fill_leaves_a_refused_allocation_alone() {
+    CHECK(smvp_test_fill_allocations(2, 0, -1) == 0);
+    const Fills a = fills();
+    const long long sets = g_memsets.load();
+    void *p = (void *)&a, *h = (void *)&a;
+    smvp_test_fail_device_alloc(1);
+    smvp_test_fail_host_alloc(1);
+    CHECK(__wrap_hipMalloc(&p, 16) == hipErrorOutOfMemory && p == nullptr);
+    CHECK(__wrap_hipHostMalloc(&h, 16, 0) == hipErrorOutOfMemory && h == nullptr);
+    const Fills b = fills();
+    CHECK(b.done() == a.done() && b.failed() == a.failed() && g_memsets.load() == sets);
+    CHECK(smvp_test_fill_allocations(0, 0, -1) == 0);
+}
+
+static void fill_window() {
+    // ordinals count device and pinned obtaining calls, refused ones too, from 0 at the arming call; [2, 4] here
+    CHECK(smvp_test_fill_allocations(1, 2, 4) == 0);
+    const Fills a = fills();
+    void *p[7] = {};
+    bool filled[7];
+    smvp_test_fail_device_alloc(3);                             // ordinal 3 is refused: it takes its ordinal with it
+    for (int i = 0; i < 7; i++) {
+        hipError_t e;
+        if (i == 1 || i == 4)
+            e = __wrap_hipHostMalloc(&p[i], 8, 0);
+        else
+            e = __wrap_hipMalloc(&p[i], 8);
+        CHECK((e == hipSuccess) == (i != 3));                   // the 3rd device call is i = 3 (i = 1 is pinned)
+        filled[i] = p[i] && holds((const unsigned char *)p[i], 8, 1);
+        if (p[i] && !filled[i])
+            std::memset(p[i], 0xAB, 8);
+    }
+    CHECK(!filled[0] && !filled[1] && filled[2] && !filled[3] && filled[4] && !filled[5] && !filled[6]);
+    CHECK(fills().done() == a.done() + 2 && fills().bytes() == a.bytes() + 16);
+    for (int i = 0; i < 7; i++)
+        CHECK((i == 1 || i == 4 ? __wrap_hipHostFree(p[i]) : __wrap_hipFree(p[i])) == hipSuccess);
+    // arming again starts the ordinals again; last < 0 has no upper end; a window of one
+    CHECK(smvp_test_fill_allocations(2, 1, 1) == 0);
+    void *q[3] = {};
+    for (int i = 0; i < 3; i++) {
+        CHECK(__wrap_hipMalloc(&q[i], 4) == hipSuccess);
+        CHECK(holds((const unsigned char *)q[i], 4, 2) == (i == 1));
+        CHECK(__wrap_hipFree(q[i]) == hipSuccess);
+    }
+    CHECK(smvp_test_fill_allocations(2, 2, -1) == 0);
+    for (int i = 0; i < 5; i++) {
+        CHECK(__wrap_hipMalloc(&q[0], 4) == hipSuccess);
+        CHECK(holds((const unsigned char *)q[0], 4, 2) == (i >= 2));
+        CHECK(__wrap_hipFree(q[0]) == hipSuccess);
+    }
+    CHECK(smvp_test_fill_allocations(0, 0, -1) == 0);
+}
+
+static void fill_that_fails() {
+    CHECK(smvp_test_fill_allocations(1, 0, -1) == 0);
+    const Fills a = fills();
+    const Snap s = snap();
+    void *p = nullptr;
+    g_fail_memsets = 1;
+    CHECK(__wrap_hipMalloc(&p, 64) == hipSuccess && p);        // the allocation's own result stands
+    CHECK(hipGetLastError() == hipSuccess);                     // the sticky error was read off
+    CHECK(g_pending.load() == 0);
+    Fills b = fills();
+    CHECK(b.failed() == a.failed() + 1 && b.done() == a.done() && b.bytes() == a.bytes());
+    CHECK(snap().at(0, LIVE) == s.at(0, LIVE) + 1 && snap().at(0, BYTES) == s.at(0, BYTES) + 64);
+    CHECK(__wrap_hipFree(p) == hipSuccess);
+    g_fail_memsets = 1;
+    CHECK(smvp_test_fill_allocations(2, 0, -1) == 0);
+    CHECK(__wrap_hipMalloc(&p, 7) == hipSuccess && p && hipGetLastError() == hipSuccess);
+    b = fills();
+    CHECK(b.failed() == a.failed() + 2 && b.done() == a.done());
+    CHECK(__wrap_hipFree(p) == hipSuccess);
+    CHECK(__wrap_hipMalloc(&p, 7) == hipSuccess && holds((const unsigned char *)p, 7, 2));      // the next one is filled as before
+    CHECK(__wrap_hipFree(p) == hipSuccess);
+    CHECK(smvp_test_fill_allocations(0, 0, -1) == 0);
+}
+
+static void fill_from_threads() {
+    CHECK(smvp_test_fill_allocations(1, 0, -1) == 0);
+    const Fills a = fills();
+    const int T = 8, ROUNDS = 500;
+    std::atomic<long long> wrong{0};
+    std::vector<std::thread> pool;
+    for (int t = 0; t < T; t++)
+        pool.emplace_back([&, t] {
+            for (int i = 0; i < ROUNDS; i++) {
+                void *p = nullptr, *h = nullptr;
+                const size_t n = (size_t)(t + 1) * 8 + (size_t)(i % 4);
+                if (__wrap_hipMalloc(&p, n) != hipSuccess || __wrap_hipHostMalloc(&h, n, 0) != hipSuccess)
+                    std::abort();
+                if (!holds((const unsigned char *)p, n, 1) || !holds((const unsigned char *)h, n, 1))
+                    wrong++;
+                (void)fills();
+                if (__wrap_hipFree(p) != hipSuccess || __wrap_hipHostFree(h) != hipSuccess)
+                    std::abort();
+            }
+        });
+    for (auto &th : pool)
+        th.join();
+    long long bytes = 0;
+    for (int t = 0; t < T; t++)
+        for (int i = 0; i < ROUNDS; i++)
+            bytes += 2 * ((t + 1) * 8 + i % 4);
+    const Fills b = fills();
+    CHECK(wrong.load() == 0);
+    CHECK(b.done() == a.done() + 2 * T * ROUNDS && b.bytes() == a.bytes() + bytes && b.failed() == a.failed());
+    CHECK(smvp_test_fill_allocations(0, 0, -1) == 0);
+}
+
 int main() {
+    fill_off_by_default();
     balance_and_bytes();
     handles();
     foreign_frees();
     nth_failure();
     threads();
+    fill_coverage();
+    fill_leaves_a_refused_allocation_alone();
+    fill_window();
+    fill_that_fails();
+    fill_from_threads();
     const Snap end = snap();
     for (int k = 0; k < 6; k++)
         CHECK(end.at(k, LIVE) == 0 && end.at(k, BYTES) == 0);

@@ -22,7 +22,8 @@ import pytest
 import oracle_binding as ob
 import smvp_toolkit_amd as sm
 from conftest import REPORTS, SAMPLES
-from parity import SPILL_KINDS, TOL, assert_spill_regime, check_guards, check_y, guarded_y, spill_matrix
+from parity import (SPILL_KINDS, TOL, assert_spill_regime, check_guards, check_y, corner_structures, csr_from_lengths, guarded_y,
+                    spill_matrix)
 from special_values import check_bits
 from test_oracle_golden import _mask
 
@@ -472,30 +473,12 @@ def test_binned_plan_corner_structures(torch):
     """The binned plan where its bookkeeping is stressed: far rows longer than a wavefront's 32 (summed by a whole
     wavefront) and longer than the cap of 1024 (kept near), rows with only far / only near entries, empty rows, more
     column blocks than a workgroup stages shifts for, duplicate and unsorted columns, a rectangular matrix."""
-    rng = np.random.default_rng(2024)
-    # wide: 3 M columns = 184 column blocks; rows of 0 ... 1500 entries, a few of them duplicates, columns NOT sorted
-    rows, cols = 6000, 3_000_000
-    lens = np.where(rng.random(rows) < 0.05, rng.integers(500, 1500, rows), rng.integers(0, 40, rows))
-    lens[:3] = (0, 1, 33)
-    row_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    col_ind = rng.integers(0, cols, int(row_ptr[-1])).astype(np.int32)
-    idx = np.arange(0, len(col_ind) - 1, 97)
-    col_ind[idx] = col_ind[idx + 1]                               # some repeats (mostly inside rows)
-    val = rng.uniform(-1, 1, len(col_ind))
-    x = rng.random(cols)
-    ref = ob.csr_spmv(row_ptr, col_ind, val, x)
-    scale = row_scale(row_ptr, col_ind, val, x)
-    for band in (0, 5, 2_000_000):
-        y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_BINNED, band)
-        check_y(y, ref, scale, np.diff(row_ptr))
-    # tall and narrow: every column within a few blocks, many far rows per row block, rows == 0 far entries in stretches
-    rows, cols = 200_000, 40_000
-    lens = rng.integers(0, 9, rows)
-    lens[50_000:90_000] = 0
-    row_ptr, col_ind, val = csr_from_lengths(rng, lens.tolist(), cols)
-    x = rng.random(cols)
-    y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_BINNED, 16)
-    check_y(y, ob.csr_spmv(row_ptr, col_ind, val, x), row_scale(row_ptr, col_ind, val, x), np.diff(row_ptr))
+    for name, rows, cols, bands, row_ptr, col_ind, val, x in corner_structures():     # (parity.py: tests/fresh_memory_scenarios.py multiplies them too)
+        ref = ob.csr_spmv(row_ptr, col_ind, val, x)
+        scale = row_scale(row_ptr, col_ind, val, x)
+        for band in bands:
+            y = gpu_csr(torch, rows, cols, row_ptr, col_ind, val, x, sm.CSR_KERNEL_BINNED, band)
+            check_y(y, ref, scale, np.diff(row_ptr))
 
 
 @pytest.mark.parametrize("kind", SPILL_KINDS)
@@ -887,15 +870,6 @@ def test_tjds_ref_quirks_reproduce_committed_reports(torch, name):
 
 
 # ------------------------------------------------------------------- edge cases
-def csr_from_lengths(rng, lens, cols):
-    rows = len(lens)
-    row_ptr = np.zeros(rows + 1, dtype=np.int32)
-    np.cumsum(lens, out=row_ptr[1:])
-    col_ind = np.concatenate([np.sort(rng.choice(cols, size=l, replace=False)) for l in lens] + [np.zeros(0, int)])
-    val = rng.uniform(-1, 1, int(row_ptr[-1]))
-    return row_ptr, col_ind.astype(np.int32), val
-
-
 EDGE_CASES = {
     "empty_matrix": lambda rng: ([0, 0, 0, 0], 5),
     "single_entry": lambda rng: ([1], 1),

@@ -19,7 +19,7 @@ COUNTED = os.path.join(PKG, "lib", "libsmvp_amd_counted.so")
 CHECK = os.path.join(PKG, "build", "san", "resource_count_check")
 OBTAINS = re.compile(r"^hip.*(Malloc|Alloc|Create|Instantiate|EndCapture)")
 TEST_EXPORTS = {"smvp_test_resources", "smvp_test_fail_device_alloc", "smvp_test_fail_host_alloc", "smvp_test_fail_stream_create",
-                "smvp_test_fail_event_create"}
+                "smvp_test_fail_event_create", "smvp_test_fill_allocations", "smvp_test_fill_stats", "smvp_test_probe_fill"}
 
 
 def nm(*args):
