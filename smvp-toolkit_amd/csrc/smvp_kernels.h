@@ -23,31 +23,32 @@ constexpr int kSweepTurnCap = (1 << (16 - kSweepRowBits)) - 1;  // ... and the 1
 constexpr int kTjdsBlock = 256;     // permuted columns per work item
 constexpr int kTjdsDiagChunk = 8;   // jagged diagonals per work item
 
-// K7 (smvp_spmm.hip): k products that share one read of the matrix
+// ---- K7 - K10: the block products (smvp_spmm.hip), kSpmmMaxVectors vectors per pass ----
 constexpr int kSpmmMaxVectors = 16;    // vectors per pass (16 doubles: one 128-byte line of X per gathered column)
 constexpr int kSpmmBlockRows = 4096;   // the plan orders rows by length inside blocks of this many consecutive rows
+// K7: Y = A X for k vectors that share one read of a CSR matrix; `order` = build_spmm_order's plan
 int build_spmm_order(const int *row_ptr, int rows, int longest_row, int *order, hipStream_t stream);  // SMVP status
 hipError_t launch_csr_spmm(const int *row_ptr, const int *col_ind, const double *val, const int *order, const double *X,
                            long long ldx, double *Y, long long ldy, int rows, int k, hipStream_t stream);
-void spmm_kernel_name(int k, char *name, size_t cap);  // the passes' kernel symbols
-
-// K8 (smvp_tjds_transposed.hip): y = A^T x from the TJDS arrays -- lane k sums permuted column k and stores y[perm[k]]
-hipError_t launch_tjds_transposed(const int *start_pos, const int *row_ind, const double *val, const int *perm, const double *x,
-                                  double *y, int cols, int num_diag, hipStream_t stream);
-const char *tjds_transposed_kernel_name();
-// K9 (smvp_tjds_spmm_transposed.hip): Y = A^T X for k vectors -- a group of G lanes sums permuted column c for G vectors and
-// stores Y(perm[c], v); kSpmmMaxVectors vectors per pass
-hipError_t launch_tjds_spmm_transposed(const int *start_pos, const int *row_ind, const double *val, const int *perm, const double *X,
-                                       long long ldx, double *Y, long long ldy, int cols, int num_diag, int k, hipStream_t stream);
-void tjds_spmm_transposed_kernel_name(int k, char *name, size_t cap);  // the passes' kernel symbols
-// K10 (smvp_tjds_spmm.hip): Y = A X for k vectors from a TJDS handle -- K7's walk over the entries regrouped by row, the value
-// read through the entry's TJDS position; kSpmmMaxVectors vectors per pass.  The plan: ptr[rows + 1], pos[nnz] (TJDS positions,
-// ascending inside a row), col[nnz] (original columns), order[rows] (build_spmm_order on ptr), all built on the device
+// K10: Y = A X for k vectors from a TJDS handle -- K7's walk over the entries regrouped by row, the value read through the
+// entry's TJDS position.  The plan: ptr[rows + 1], pos[nnz] (TJDS positions, ascending inside a row), col[nnz] (original
+// columns), order[rows] (build_spmm_order on ptr), all built on the device
 int build_tjds_spmm_plan(const int *row_ind, const int *start_pos, const int *perm, int num_diag, int nnz, int rows, int *ptr,
                          int *pos, int *col, int *order, hipStream_t stream);  // SMVP status; synchronises `stream`
 hipError_t launch_tjds_spmm(const int *ptr, const int *pos, const int *col, const double *val, const int *order, const double *X,
                             long long ldx, double *Y, long long ldy, int rows, int k, hipStream_t stream);
-void tjds_spmm_kernel_name(int k, char *name, size_t cap);  // the passes' kernel symbols
+// K8: y = A^T x from the TJDS arrays -- lane k sums permuted column k and stores y[perm[k]]
+hipError_t launch_tjds_transposed(const int *start_pos, const int *row_ind, const double *val, const int *perm, const double *x,
+                                  double *y, int cols, int num_diag, hipStream_t stream);
+// K9: Y = A^T X for k vectors -- a group of G lanes sums permuted column c for G vectors and stores Y(perm[c], v)
+hipError_t launch_tjds_spmm_transposed(const int *start_pos, const int *row_ind, const double *val, const int *perm, const double *X,
+                                       long long ldx, double *Y, long long ldy, int cols, int num_diag, int k, hipStream_t stream);
+// the passes' kernel symbols, "name<G> + name<G> + ..." cut to `cap`
+void spmm_kernel_name(int k, char *name, size_t cap);
+void tjds_spmm_kernel_name(int k, char *name, size_t cap);
+void tjds_spmm_transposed_kernel_name(int k, char *name, size_t cap);
+const char *tjds_transposed_kernel_name();
+
 // K14 (smvp_diagonal.hip): d[i] = the stored entries (i, i) added in storage order from +0.0.  CSR: a group of lanes_per_row lanes
 // (2 .. 64, a power of two) per row, the diagonal of row r at column first_row + r; TJDS: lane k walks permuted column k
 hipError_t launch_csr_diagonal(int lanes_per_row, const int *row_ptr, const int *col_ind, const double *val, double *d, int rows,

@@ -43,7 +43,7 @@ __device__ __forceinline__ double shfl_down_sum(double v)
 // (one XCD per contiguous eighth of the matrix was 60.1 %).  64 keeps the speed of
 // the small groups and most of the traffic saving of the large ones.
 // Speed only: any placement gives the same result.  (tile_of_block itself lives in
-// smvp_tile_map.h: K7, smvp_spmm.hip, deals its row blocks the same way.)
+// smvp_tile_map.h: K7 and K10, smvp_spmm.hip, deal their row blocks the same way.)
 // The owner kernel deals its tiles in either direction, tile_of_block_swept: the plain launches of a
 // handle whose matrix is larger than the 256 MiB Infinity Cache alternate, so a product starts on the
 // tiles the one before it touched last -- what the cache still holds (DESIGN.md section 4, K2:

@@ -50,7 +50,7 @@ struct TwoPhasePlan {
     smvp_csr_t *csr = nullptr;  // the tile-ordered stream over (inv_ptr, inv_pos) with prod as its values, no operand
 };
 
-// smvp_tjds_spmm (K10, smvp_tjds_spmm.hip): the entries regrouped by row in buffers of its own (not the two plans' above: they
+// smvp_tjds_spmm (K10, smvp_spmm.hip): the entries regrouped by row in buffers of its own (not the two plans' above: they
 // come and go with the modes), built by the first call and kept whatever the mode is
 struct TjdsSpmmPlan {
     int *d_ptr = nullptr;    // rows + 1

@@ -575,6 +575,23 @@ def spmm_operands(X, Y, rows, cols):
     return k, X.stride(0), Y.stride(0)
 
 
+def _spmm(fn, handle, X, Y, out_rows, in_rows, stream):
+    """smvp_csr_spmm / smvp_tjds_spmm / smvp_tjds_spmm_transposed: X of in_rows and Y of out_rows rows, checked by spmm_operands."""
+    k, ldx, ldy = spmm_operands(X, Y, out_rows, in_rows)
+    if not (X.is_cuda and Y.is_cuda):
+        raise ValueError("X and Y must be device tensors")
+    _check(getattr(lib(), fn)(handle, k, _dev_ptr(X), ldx, _dev_ptr(Y), ldy, _stream_ptr(stream)), fn)
+
+
+def _spmm_describe(fn, handle, k, with_plan):
+    """The describe call of a block product -> (kernel symbols, algorithmic bytes for k vectors) and, with_plan, {plan_bytes,
+    build_ms} of its plan."""
+    name, b, i = C.create_string_buffer(256), C.c_double(), PlanInfo()
+    _check(getattr(lib(), fn)(handle, k, name, 256, C.byref(b), *([C.byref(i)] if with_plan else [])), fn)
+    plan = ({"plan_bytes": i.plan_bytes, "build_ms": i.build_ms},) if with_plan else ()
+    return (name.value.decode(), b.value) + plan
+
+
 def transposed_operands(x, y, rows, cols):
     """Checks the operands of TjdsMatrix.spmv_transposed: x of `rows` and y of `cols` float64 elements, contiguous tensors.
     Raises ValueError otherwise.  Checks dtype, size and strides only, so it runs on CPU tensors too."""
@@ -974,18 +991,11 @@ class CsrMatrix:
         """Y = A X for k vectors at once (smvp_csr_spmm): X (cols x k) and Y (rows x k) are float64 CUDA tensors with
         stride(1) == 1, ldx = X.stride(0), ldy = Y.stride(0).  Every column of Y is the serial loop's bits.  Asynchronous on
         `stream`; the first call builds the plan."""
-        k, ldx, ldy = spmm_operands(X, Y, self.rows, self.cols)
-        if not (X.is_cuda and Y.is_cuda):
-            raise ValueError("X and Y must be device tensors")
-        _check(lib().smvp_csr_spmm(self._h, k, _dev_ptr(X), ldx, _dev_ptr(Y), ldy, _stream_ptr(stream)), "smvp_csr_spmm")
+        _spmm("smvp_csr_spmm", self._h, X, Y, self.rows, self.cols, stream)
 
     def spmm_describe(self, k):
         """(kernel symbols, algorithmic bytes for k vectors, {plan_bytes, build_ms} of the SpMM plan: 0 before the first spmm)."""
-        name = C.create_string_buffer(256)
-        b = C.c_double()
-        i = PlanInfo()
-        _check(lib().smvp_csr_spmm_describe(self._h, k, name, 256, C.byref(b), C.byref(i)), "smvp_csr_spmm_describe")
-        return name.value.decode(), b.value, {"plan_bytes": i.plan_bytes, "build_ms": i.build_ms}
+        return _spmm_describe("smvp_csr_spmm_describe", self._h, k, True)
 
     @classmethod
     def _wrap(cls, handle, rows, cols, nnz, owner=None):
@@ -1116,35 +1126,21 @@ class TjdsMatrix:
         """Y = A^T X for k vectors at once from the TJDS arrays themselves (smvp_tjds_spmm_transposed, K9): X (rows x k) and
         Y (cols x k) are float64 CUDA tensors with stride(1) == 1, ldx = X.stride(0), ldy = Y.stride(0).  Every column of Y is
         the transposed product's bits.  Asynchronous on `stream`; needs no set_x and no plan."""
-        k, ldx, ldy = spmm_operands(X, Y, self.cols, self.rows)
-        if not (X.is_cuda and Y.is_cuda):
-            raise ValueError("X and Y must be device tensors")
-        _check(lib().smvp_tjds_spmm_transposed(self._h, k, _dev_ptr(X), ldx, _dev_ptr(Y), ldy, _stream_ptr(stream)),
-               "smvp_tjds_spmm_transposed")
+        _spmm("smvp_tjds_spmm_transposed", self._h, X, Y, self.cols, self.rows, stream)
 
     def spmm_transposed_describe(self, k):
         """(kernel symbols, algorithmic bytes for k vectors) of spmm_transposed."""
-        name = C.create_string_buffer(256)
-        b = C.c_double()
-        _check(lib().smvp_tjds_spmm_transposed_describe(self._h, k, name, 256, C.byref(b)), "smvp_tjds_spmm_transposed_describe")
-        return name.value.decode(), b.value
+        return _spmm_describe("smvp_tjds_spmm_transposed_describe", self._h, k, False)
 
     def spmm(self, X, Y, stream=None):
         """Y = A X for k vectors at once from a TJDS handle (smvp_tjds_spmm, K10): X (cols x k) and Y (rows x k) are float64
         CUDA tensors with stride(1) == 1, ldx = X.stride(0), ldy = Y.stride(0).  Every column of Y is the serial sum over the
         row in TJDS position order.  Asynchronous on `stream`; needs no set_x; the first call builds the plan."""
-        k, ldx, ldy = spmm_operands(X, Y, self.rows, self.cols)
-        if not (X.is_cuda and Y.is_cuda):
-            raise ValueError("X and Y must be device tensors")
-        _check(lib().smvp_tjds_spmm(self._h, k, _dev_ptr(X), ldx, _dev_ptr(Y), ldy, _stream_ptr(stream)), "smvp_tjds_spmm")
+        _spmm("smvp_tjds_spmm", self._h, X, Y, self.rows, self.cols, stream)
 
     def spmm_describe(self, k):
         """(kernel symbols, algorithmic bytes for k vectors, {plan_bytes, build_ms} of the SpMM plan: 0 before the first spmm)."""
-        name = C.create_string_buffer(256)
-        b = C.c_double()
-        i = PlanInfo()
-        _check(lib().smvp_tjds_spmm_describe(self._h, k, name, 256, C.byref(b), C.byref(i)), "smvp_tjds_spmm_describe")
-        return name.value.decode(), b.value, {"plan_bytes": i.plan_bytes, "build_ms": i.build_ms}
+        return _spmm_describe("smvp_tjds_spmm_describe", self._h, k, True)
 
     def set_mode(self, mode):
         _check(lib().smvp_tjds_set_mode(self._h, mode), "smvp_tjds_set_mode")
