@@ -1094,6 +1094,100 @@ int smvp_tjds_pbicgstab(smvp_tjds_t *h, const smvp_bicgstab_opts_t *opts, const 
                         smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_bicgstab_result_t *result, double *rr_each,
                         double *ss_each, void *stream);
 
+/* ------------------------------------------------- restarted GMRES */
+/* Right-preconditioned restarted GMRES(m) on a square n x n handle's own product, kernel K19 (new: the reference only multiplies):
+ * what a caller reaches for when BiCGSTAB above stalls or breaks down.  It minimises the residual over the Krylov space, so the
+ * estimate never rises inside a cycle.  The orthogonalisation is classical Gram-Schmidt applied twice ("CGS2"): a fixed sequence of
+ * launches that needs no host decision.  M = T1 diag(m)^-1 T2 is exactly K18's and yhat = M^-1 y is computed as there; each of
+ * first, d_m and second may be NULL, and ALL THREE NULL IS ALLOWED HERE: that is plain GMRES (z = v_j, no launch).  `dot` is the one
+ * above, unchanged; every other operation is one correctly rounded IEEE operation, on an element or on a scalar, with no FMA;
+ * sqrt is the correctly rounded IEEE root.
+ *   bb = dot(b, b)      thr = (tol * tol) * bb          (as K13)
+ *   x = d_x0, or zeros if NULL;   k = 0 (steps done)
+ *   cycle c = 0, 1, ...:
+ *     r = b - A x                 (cycle 0 with d_x0 == NULL: r = b bit for bit, no product)
+ *     tr_c = dot(r, r)            -> restart_each[c];  for c = 0 also rr_each[0]
+ *     start rule:  NONFINITE if bb or tr_c is NaN or +-Inf;  CONVERGED if tr_c <= thr        -> x as it stands, columns = 0
+ *     beta = sqrt(tr_c)    v_1 = r / beta  (true division per element)    g_1 = beta
+ *     for j = 1 .. restart:       k = k + 1
+ *       z = M^-1 v_j   (z = v_j without M)          w = A z   (the handle's own product, bit for bit)
+ *       h_i  = dot(v_i, w)                 i = 1 .. j      (each one is `dot`'s bits)
+ *       w    = w - h_i * v_i   for i = 1 .. j ascending    (product rounded, difference rounded, per element)
+ *       q_i  = dot(v_i, w)                 i = 1 .. j      (second pass, on the updated w)
+ *       w    = w - q_i * v_i   for i = 1 .. j ascending
+ *       h_i  = h_i + q_i                                   (one rounded addition)
+ *       h_{j+1} = sqrt(dot(w, w))
+ *       for i = 1 .. j-1:  t = (c_i*h_i) + (s_i*h_{i+1});  h_{i+1} = (c_i*h_{i+1}) - (s_i*h_i);  h_i = t
+ *       d = sqrt((h_j*h_j) + (h_{j+1}*h_{j+1}))
+ *       rule S1:  NONFINITE if any of h_1 .. h_{j+1} (before the rotations) or d is NaN or +-Inf;  BREAKDOWN if d == 0
+ *                                                                                            -> update with columns = j - 1
+ *       c_j = h_j / d    s_j = h_{j+1} / d    R_{1..j-1, j} = h_{1..j-1}    R_{jj} = d
+ *       g_{j+1} = -(s_j * g_j)     g_j = c_j * g_j         rr_k = g_{j+1} * g_{j+1}  -> rr_each[k]
+ *       rule S2 (first that holds):  CONVERGED if rr_k <= thr;  MAX_STEPS if k == max_steps  -> update with columns = j
+ *       v_{j+1} = w / h_{j+1}
+ *     (j == restart without a stop: update with columns = restart, next cycle)
+ *   update with `cols` columns (nothing for cols = 0):
+ *     y_i for i = cols .. 1:  acc = g_i;  for l = i+1 .. cols ascending: acc = acc - (R_il * y_l);  y_i = acc / R_ii
+ *     u = y_1 * v_1;  u = u + (y_i * v_i) for i = 2 .. cols ascending;   x = x + M^-1 u
+ * Squared norms: the histories and the result hold squared residual norms, as everywhere.  Happy breakdown: h_{j+1} == 0 needs no
+ * rule -- it gives s_j = 0 and rr_k = +0.0 <= thr, hence CONVERGED; v_{j+1} is only formed after S2 has passed.  No scaling is done
+ * against overflow of the squares: that case shows as NONFINITE.  rr_k is the recurrence's estimate of the residual of the ORIGINAL
+ * system, because the preconditioning is on the right, so tol means what it means for K13 and K18; tr_c is a true residual, which
+ * every restart gets for free.  bb, every tr_c and every rr_k are never -0.0.  Nothing of M is validated, as for K18.
+ * The device evaluates the rules at EVERY step and at every cycle start; after a stop nothing more is written to x, the basis, R, g
+ * or the histories.  The host reads a status block at looked steps only -- step 0, every k with k % check_every == 0, and
+ * k == max_steps -- and only to leave the loop: every result, both histories and every bit of d_x do not depend on check_every.
+ * The update of x at a stop in mid-cycle has no fixed place in the enqueued sequence: the update launches enqueued at a cycle's end
+ * act only while the run has not stopped, and once the host has seen the stop it enqueues the same launches once more, told to act
+ * on the stopped cycle's columns; nothing they read has changed since.  No kernel waits on a value another workgroup writes; no
+ * atomics, no flags; every scalar hand-off is a launch boundary.
+ * Out of scope: the basis is non-flexible (the update applies M^-1 once to V y; no second basis is stored); left or split
+ * preconditioning, flexible GMRES, deflation, a single-pass or modified Gram-Schmidt variant, several right-hand sides and the
+ * sharded handles. */
+enum { SMVP_GMRES_CONVERGED = 0, SMVP_GMRES_MAX_STEPS = 1, SMVP_GMRES_BREAKDOWN = 2, SMVP_GMRES_NONFINITE = 3 };
+typedef struct smvp_gmres_opts {
+    unsigned struct_size; /* set by smvp_gmres_opts_default, checked as for smvp_cg_opts_t */
+    int max_steps;        /* >= 1; default 100 */
+    int check_every;      /* >= 1; default 10 */
+    int restart;          /* 1 .. 64; default 30: the columns of a cycle */
+    double tol;           /* >= 0, finite; default 1e-10: stop at |r| <= tol |b| */
+} smvp_gmres_opts_t;
+void smvp_gmres_opts_default(smvp_gmres_opts_t *o);
+typedef struct smvp_gmres_result {
+    int steps;   /* steps done: products with a basis vector (those for a cycle's r are not counted) */
+    int cycles;  /* cycles started */
+    int columns; /* of the last update: j or j - 1 of the step that stopped the run, 0 after a start rule */
+    int reason;  /* SMVP_GMRES_* */
+    double rr;   /* rr_steps; tr_c after a start rule, or where rule S1 fired in a cycle's first step */
+    double bb;   /* dot(b, b) */
+} smvp_gmres_result_t;
+/*   - d_b, d_x0, d_x, d_m, first and second as for smvp_csr_pbicgstab: d_x may be d_x0, any other overlap of d_x with d_x0, d_b
+ *     or d_m is SMVP_ERR_INVALID; the plans are smvp_csr_trsv_create's on any plain-CSR handle of n rows on the handle's device.
+ *   - rr_each: a caller-owned HOST array of max_steps + 1 doubles, filled 0 .. steps (0 .. steps - 1 where rule S1 ended the run).
+ *     restart_each: ceil(max_steps / restart) + 1 doubles, filled 0 .. cycles - 1.  Either may be NULL; both are left untouched
+ *     beyond the filled elements.
+ *   - The call returns after the work on `stream` has finished.  It allocates its workspace per call and frees it on every way
+ *     out: min(restart, max_steps) + 1 basis vectors, then w, u, z and r; the partials of `restart` dots (2048 doubles each) and of
+ *     dot(w, w), dot(r, r) and dot(b, b), then R, c, s, g, y, the coefficient words, the histories and two status blocks.
+ *   - Beside the product and the solves' own launches step j of a cycle is six launches: the multi-dot (v_1 .. v_j read once, w
+ *     once per 4 coefficients), a fold of one workgroup per coefficient, the first update with the second pass's partials (the basis
+ *     read twice, w read, written and read back), a fold, the second update with dot(w, w)'s partials (the basis read once, w read
+ *     and written), and the close of the step (w read, v_{j+1} written): 4 j + 6 + 2 ceil(j / 4) passes over a vector.  An update
+ *     of x is a one-lane back-substitution, one pass over `cols` basis vectors, the solves, and x = x + z; a cycle's start is one
+ *     product and two launches.
+ *   - SMVP_ERR_INVALID and SMVP_ERR_UNSUPPORTED as for smvp_csr_pbicgstab, except that first, d_m and second all NULL is accepted;
+ *     restart outside 1 .. 64 is SMVP_ERR_INVALID.  Nothing is enqueued then, d_x and *result are left untouched, and a capturing
+ *     stream's capture stays valid.
+ *   - n == 0: SMVP_OK, steps 0, cycles 0, columns 0, reason SMVP_GMRES_CONVERGED, rr = bb = +0.0.
+ *   - State: the handle and the plans as after smvp_csr_pbicgstab / smvp_tjds_pbicgstab: a CSR handle's plan is untouched, a TJDS
+ *     handle needs smvp_tjds_set_x again, smvp_trsv_solve gives the bits it gave before. */
+int smvp_csr_gmres(smvp_csr_t *h, const smvp_gmres_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                   smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_gmres_result_t *result, double *rr_each,
+                   double *restart_each, void *stream);
+int smvp_tjds_gmres(smvp_tjds_t *h, const smvp_gmres_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                    smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_gmres_result_t *result, double *rr_each,
+                    double *restart_each, void *stream);
+
 /* ------------------------------------------- several GPUs, one host process */
 /* New design (the reference is one CPU thread): the matrix is cut into `ngpus` row blocks balanced by entries
  * (smvp_partition_rows); GPU g holds block g -- cut again into `chunks` row chunks, each its own CSR / TJDS handle --

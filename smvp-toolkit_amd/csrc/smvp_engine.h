@@ -188,8 +188,8 @@ int power_check_args(const char *fn, const void *h, const smvp_power_opts_t *opt
 int power_run(const char *fn, int device, int rows, int cols, const smvp_power_opts_t *opts, const double *d_x0, double *d_x,
               smvp_power_result_t *result, double *lambda_each, double *residual_each, void *stream, const HandleProduct &product);
 
-// ------------------------------------------------------------------------------- the Krylov solvers (K12 to K14, K16, K18)
-// smvp_cg.hip and smvp_bicgstab.hip run the steps around the same product hook, checked and handed over by the handle files as for
+// ------------------------------------------------------------------------------- the Krylov solvers (K12 to K14, K16, K18, K19)
+// smvp_cg.hip, smvp_bicgstab.hip and smvp_gmres.hip run the steps around the same product hook, checked and handed over by the handle files as for
 // K11.  The *_check_args make no HIP call; the *_run check the plans, the operands and the stream, then allocate, iterate and free.
 // A preconditioner is M = T1 diag(m)^-1 T2: z = T2^-1 (m .* (T1^-1 r)), any part may be missing.  The plans are K15's
 // (smvp_trsv.hip): trsv_enqueue is the launch loop smvp_trsv_solve itself goes through, with the operands checked and the plan's
@@ -223,5 +223,11 @@ int pbicgstab_check_args(const char *fn, const void *h, const smvp_bicgstab_opts
 int bicgstab_run(const char *fn, int device, int rows, int cols, const smvp_bicgstab_opts_t *opts, const double *d_b, const double *d_x0,
                  double *d_x, const KrylovPrecond *M, smvp_bicgstab_result_t *result, double *rr_each, double *ss_each, void *stream,
                  const HandleProduct &product);
+
+// restarted GMRES (K19, smvp_gmres.hip), one product a step.  M with all three parts NULL is plain GMRES.
+int gmres_check_args(const char *fn, const void *h, const smvp_gmres_opts_t *opts, const smvp_gmres_result_t *result, const double *d_b);
+int gmres_run(const char *fn, int device, int rows, int cols, const smvp_gmres_opts_t *opts, const double *d_b, const double *d_x0,
+              double *d_x, const KrylovPrecond &M, smvp_gmres_result_t *result, double *rr_each, double *restart_each, void *stream,
+              const HandleProduct &product);
 
 }  // namespace smvp

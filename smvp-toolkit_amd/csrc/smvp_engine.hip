@@ -983,7 +983,8 @@ extern "C" int smvp_csr_spmv(smvp_csr_t *h, const double *d_x, double *d_y, void
     return smvp::csr_spmv_stamped(h, d_x, d_y, stream, nullptr);
 }
 
-// What the solvers on a CSR handle (K11 to K14, K16, K18; the steps are smvp_power.hip's, smvp_cg.hip's and smvp_bicgstab.hip's) share: the
+// What the solvers on a CSR handle (K11 to K14, K16, K18, K19; the steps are smvp_power.hip's, smvp_cg.hip's, smvp_bicgstab.hip's and
+// smvp_gmres.hip's) share: the
 // product is smvp_csr_spmv's on the current plan, which it leaves as it is, and a handle that belongs to a TJDS matrix is refused.
 static smvp::HandleProduct csr_product(smvp_csr_t *h, void *stream)
 {
@@ -1089,6 +1090,18 @@ extern "C" int smvp_csr_pbicgstab(smvp_csr_t *h, const smvp_bicgstab_opts_t *opt
         return rc;
     return smvp::bicgstab_run("smvp_csr_pbicgstab", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, &M, result, rr_each, ss_each, stream,
                               csr_product(h, stream));
+}
+
+extern "C" int smvp_csr_gmres(smvp_csr_t *h, const smvp_gmres_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                              smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_gmres_result_t *result, double *rr_each,
+                              double *restart_each, void *stream)
+{
+    if (int rc = smvp::gmres_check_args("smvp_csr_gmres", h, opts, result, d_b))
+        return rc;
+    if (int rc = refuse_tjds_flavor("smvp_csr_gmres", h))
+        return rc;
+    return smvp::gmres_run("smvp_csr_gmres", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, smvp::KrylovPrecond{first, d_m, second}, result,
+                           rr_each, restart_each, stream, csr_product(h, stream));
 }
 
 // the owner kernel, whose launch can time itself on the device?

@@ -117,6 +117,14 @@ class BicgstabResult(C.Structure):
     _fields_ = [("steps", C.c_int), ("full", C.c_int), ("half", C.c_int), ("reason", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
 
 
+class GmresOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("max_steps", C.c_int), ("check_every", C.c_int), ("restart", C.c_int), ("tol", C.c_double)]
+
+
+class GmresResult(C.Structure):
+    _fields_ = [("steps", C.c_int), ("cycles", C.c_int), ("columns", C.c_int), ("reason", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
+
+
 class TrsvInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("levels", C.c_int), ("max_level_width", C.c_int), ("launches", C.c_int), ("chains", C.c_int),
                 ("chain_width", C.c_int), ("missing_diagonals", C.c_int), ("lanes_per_row", C.c_int), ("entries", C.c_longlong),
@@ -134,6 +142,7 @@ TRSV_LOWER, TRSV_UPPER = 0, 1
 TRSV_DIAG_STORED, TRSV_DIAG_UNIT = 0, 1
 CG_CONVERGED, CG_MAX_STEPS, CG_BREAKDOWN, CG_NONFINITE = 0, 1, 2, 3
 BICGSTAB_CONVERGED, BICGSTAB_MAX_STEPS, BICGSTAB_BREAKDOWN, BICGSTAB_NONFINITE = 0, 1, 2, 3
+GMRES_CONVERGED, GMRES_MAX_STEPS, GMRES_BREAKDOWN, GMRES_NONFINITE = 0, 1, 2, 3
 GATHER_NONE, GATHER_OVERLAPPED, GATHER_AFTER = 0, 1, 2
 EXCHANGE_RCCL, EXCHANGE_COPIES, EXCHANGE_DIRECT, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGE_NAMES = {EXCHANGE_RCCL: "rccl", EXCHANGE_COPIES: "copies", EXCHANGE_DIRECT: "direct", EXCHANGE_AUTO: "auto"}
@@ -174,6 +183,7 @@ EXPORTS = [
     "smvp_csr_trsv_create", "smvp_trsv_solve", "smvp_trsv_info", "smvp_trsv_schedule", "smvp_trsv_destroy", "smvp_csr_trsv_levels",
     "smvp_csr_pcg_tri", "smvp_tjds_pcg_tri",
     "smvp_csr_pbicgstab", "smvp_tjds_pbicgstab",
+    "smvp_gmres_opts_default", "smvp_csr_gmres", "smvp_tjds_gmres",
     "smvp_csr_ilu0_create", "smvp_ilu0_factor", "smvp_ilu0_matrix", "smvp_ilu0_info", "smvp_ilu0_destroy", "smvp_csr_ilu0_check",
     "smvp_csr_ilu0_host",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
@@ -251,6 +261,10 @@ def lib():
         L.smvp_tjds_pcg_tri.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
         L.smvp_csr_pbicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
         L.smvp_tjds_pbicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
+        L.smvp_gmres_opts_default.argtypes = [C.POINTER(GmresOpts)]
+        L.smvp_gmres_opts_default.restype = None
+        L.smvp_csr_gmres.argtypes = [vp, C.POINTER(GmresOpts), vp, vp, vp, vp, vp, vp, C.POINTER(GmresResult), vp, vp, vp]
+        L.smvp_tjds_gmres.argtypes = [vp, C.POINTER(GmresOpts), vp, vp, vp, vp, vp, vp, C.POINTER(GmresResult), vp, vp, vp]
         L.smvp_csr_ilu0_create.argtypes = [C.POINTER(vp), vp, vp]
         L.smvp_ilu0_factor.argtypes = [vp, vp]
         L.smvp_ilu0_matrix.argtypes = [vp, C.POINTER(vp)]
@@ -800,6 +814,39 @@ def _pbicgstab(fn, handle, b, x, first, second, m, x0, max_steps, tol, check_eve
     return r, rr[:r.full + 1], ss[:filled]
 
 
+def gmres_opts(max_steps=100, tol=1e-10, check_every=10, restart=30):
+    """smvp_gmres_opts_t from smvp_gmres_opts_default with the four fields set."""
+    o = GmresOpts()
+    lib().smvp_gmres_opts_default(C.byref(o))
+    o.max_steps, o.check_every, o.restart, o.tol = int(max_steps), int(check_every), int(restart), float(tol)
+    return o
+
+
+def _gmres(fn, handle, b, x, first, second, m, x0, restart, max_steps, tol, check_every, stream):
+    """smvp_csr_gmres / smvp_tjds_gmres -> (GmresResult, rr_each, restart_each), the histories cut to the filled elements.  rr_each
+    has result.steps + 1 elements, one fewer where rule S1 ended the run: the result block does not say which, so the array starts
+    as -0.0, which no rr can be, and an element left so was not filled.  first and second are open TrsvPlans or None; m may be None;
+    all three None is plain GMRES."""
+    for name, t in (("first", first), ("second", second)):
+        if t is None:
+            continue
+        if not isinstance(t, TrsvPlan):
+            raise ValueError("%s must be a TrsvPlan or None, not %s" % (name, type(t).__name__))
+        if not t._t:
+            raise ValueError("%s is a closed TrsvPlan" % name)
+    _device_vectors(b=b, x=x, m=m, x0=x0)
+    o = gmres_opts(max_steps, tol, check_every, restart)
+    r = GmresResult()
+    steps, every = max(int(max_steps), 1), min(max(int(restart), 1), 64)
+    rr, tr = np.full(steps + 1, -0.0), np.full(-(-steps // every) + 1, -0.0)
+    _check(getattr(lib(), fn)(handle, C.byref(o), _dev_ptr(b), _dev_ptr(x0), _dev_ptr(x), first._t if first else None, _dev_ptr(m),
+                              second._t if second else None, C.byref(r), _p(rr), _p(tr), _stream_ptr(stream)), fn)
+    filled = r.steps + 1
+    if filled > 1 and rr[filled - 1] == 0.0 and np.signbit(rr[filled - 1]):
+        filled -= 1
+    return r, rr[:filled], tr[:r.cycles]
+
+
 def ilu0_check(rows, row_ptr, col_ind):
     """diag_pos, the position of every row's (i, i), for CSR arrays on the host that admit an ILU(0) (smvp_csr_ilu0_check, K17):
     every row's columns strictly ascending, a stored diagonal in every row.  Raises SmvpError otherwise; its bad_row attribute is the
@@ -987,6 +1034,14 @@ class CsrMatrix:
         ss_each).  With plans, choose a small check_every: a step enqueued in vain runs four solves."""
         return _pbicgstab("smvp_csr_pbicgstab", self._h, b, x, first, second, m, x0, max_steps, tol, check_every, stream)
 
+    def gmres(self, b, x, first=None, second=None, m=None, x0=None, restart=30, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Right-preconditioned restarted GMRES(restart) for A x = b with M = T1 diag(m)^-1 T2 (smvp_csr_gmres, K19; A any square
+        matrix): the preconditioner as for pbicgstab, and all of first, second and m None is plain GMRES.  restart is 1 .. 64.
+        Returns (GmresResult, rr_each, restart_each) after the work on `stream` has finished: rr_each holds tr_0 and the estimate
+        of the squared residual norm after every step, restart_each the true squared residual norm at every cycle's start.
+        Nothing depends on check_every but how often the host waits."""
+        return _gmres("smvp_csr_gmres", self._h, b, x, first, second, m, x0, restart, max_steps, tol, check_every, stream)
+
     def spmm(self, X, Y, stream=None):
         """Y = A X for k vectors at once (smvp_csr_spmm): X (cols x k) and Y (rows x k) are float64 CUDA tensors with
         stride(1) == 1, ldx = X.stride(0), ldy = Y.stride(0).  Every column of Y is the serial loop's bits.  Asynchronous on
@@ -1105,6 +1160,12 @@ class TjdsMatrix:
         ROW_GATHER or TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.pbicgstab.  The plans belong to CsrMatrix
         objects; Jacobi (m = 1 / diagonal() alone) needs none."""
         return _pbicgstab("smvp_tjds_pbicgstab", self._h, b, x, first, second, m, x0, max_steps, tol, check_every, stream)
+
+    def gmres(self, b, x, first=None, second=None, m=None, x0=None, restart=30, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """Right-preconditioned restarted GMRES(restart) for A x = b on this handle's product in its current mode (smvp_tjds_gmres,
+        K19; ROW_GATHER or TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.gmres.  The plans belong to CsrMatrix
+        handles; afterwards the handle's permuted operand is the last vector multiplied: call set_x again."""
+        return _gmres("smvp_tjds_gmres", self._h, b, x, first, second, m, x0, restart, max_steps, tol, check_every, stream)
 
     def spmv_transposed(self, x, y, stream=None):
         """y = A^T x from the TJDS arrays themselves (smvp_tjds_spmv_transposed, K8): x of `rows`, y of `cols` float64 CUDA
