@@ -67,6 +67,9 @@ const char *smvp_version_string(void); /* "0.6.4" */
  *   "csr_sweep_alternate" 0: every product of the tile kernel sweeps its tiles forward; 1: a handle's plain launches alternate
  *                            forward / backward whatever the size (default: where one product's bytes exceed the Infinity Cache);
  *                            the results are the same bits either way
+ *   "csr_read_once" 0 / 1: the plain CSR tile kernel's single launches never / always read val and the 16-bit column offsets
+ *                            with the read-once (non-temporal) hint (default: where one product's bytes exceed 1 GiB); the same
+ *                            bits either way
  *   "tjds_index" 0 | 1 | 2: 16-bit position words (default) / 32-bit sorted / 32-bit columns
  *   "sharded_threads" 1: the sharded layer's issuing threads with one GPU too     "mm_threads" n: the reader's threads (1 = serial)
  *   "trsv_chain_width" 256 | 512 | 1024: the widest level a triangular solve's chain takes (default 256), read by smvp_csr_trsv_create and

@@ -12,6 +12,7 @@
 // like the host's stable counting sorts.
 #include "smvp_common.h"
 #include "smvp_prim.h"
+#include "smvp_tile_map.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1035,13 +1036,19 @@ __global__ __launch_bounds__(256) void tile_column_spans(const int *__restrict__
     }
 }
 
+// The offsets of a full, narrow tile of 2048 entries lie in the order the tile kernel's lanes hold the entries
+// (smvp::col16_slot: a permutation inside the tile); 1024-entry tiles keep the plain order, and so do the last, partial tile
+// (the kernel's slow path reads col_ind there) and the zeros of a wide tile.  Every entry [0, nnz) of col16 is written.
 __global__ __launch_bounds__(256) void column_offsets(const int *__restrict__ col_ind, int nnz, int tile,
                                                       const int *__restrict__ col_base, unsigned short *__restrict__ col16)
 {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j < nnz) {
-        const int base = col_base[j / tile];
-        col16[j] = base < 0 ? (unsigned short)0 : (unsigned short)(col_ind[j] - base);  // a wide tile reads col_ind itself
+        const int b = j / tile, s = b * tile;
+        const int base = col_base[b];
+        const bool lane_order = tile == smvp::kCol16LaneOrderTile && base >= 0 && (long long)s + tile <= (long long)nnz;
+        const int at = lane_order ? s + smvp::col16_slot(j - s, tile / 256) : j;
+        col16[at] = base < 0 ? (unsigned short)0 : (unsigned short)(col_ind[j] - base);  // a wide tile reads col_ind itself
     }
 }
 

@@ -44,8 +44,11 @@ struct TilePlan {
     int *d_tile_next = nullptr;   // STREAM: row_ptr[first row of the next tile]
     // STREAM, plain CSR, tiles of 1024 / 2048 entries whose columns all span < 65536: col_ind a second time as 16-bit
     // offsets from the tile's smallest column (10 instead of 12 bytes per entry; csr_stream_owner<., kFlavorCsr16, .>)
+    // (at 2048-entry tiles a full narrow tile's offsets lie in the order the kernel's lanes hold its entries, smvp::col16_slot:
+    // the array serves the tile size it was laid out for, col16_tile, and no other)
     unsigned short *d_col16 = nullptr;
     int *d_col_base = nullptr;
+    int col16_tile = 0;
     // STREAM: every row's first entry as a 16-bit offset from the first entry of the tile the row
     // starts in -- what phase 2 reads instead of row_ptr (2 instead of 4 bytes per row)
     unsigned short *d_row_rel = nullptr;
@@ -71,6 +74,9 @@ struct TilePlan {
     // holds; sweep_alternate = 0 (a matrix the caches hold, or plan option "csr_sweep_alternate" 0; decided when the plan is
     // built): always forward
     int sweep_alternate = 1, sweep_backward = 0;
+    // STREAM, plain CSR: the single launches read val and the 16-bit offsets of full tiles with the read-once hint (decided when
+    // the plan is built: kReadOnceMinBytes or plan option "csr_read_once")
+    int read_once = 0;
 };
 
 // COLSWEEP: the entries a second time, every strip sorted by column (built on the device); build_sweep_plan
@@ -456,6 +462,7 @@ int try_column_offsets(smvp_csr *h)
             h->vpt = tiles[i] / smvp::kStreamBlock;
             h->tile.d_col_base = col_base;
             h->tile.d_col16 = col16;
+            h->tile.col16_tile = tiles[i];
             return SMVP_OK;
         }
     }
@@ -472,6 +479,12 @@ int try_column_offsets(smvp_csr *h)
 // lives in the L2s or in the Infinity Cache finds its lines in another XCD's L2 -- memplus x16 (30 MB) ran 27 % slower
 // alternating, x40 / x100 (75 / 187 MB) 0.8 / 0.3 % slower, x200 (374 MB) 8 % faster (profiles/sweep_direction_measured.txt).
 constexpr double kSweepAlternateMinBytes = 256.0 * 1024 * 1024;
+
+// The single launches of the plain CSR tile kernel read val -- and the 16-bit column offsets, where a lane's are one 16-byte
+// load -- with non-temporal loads where one product's algorithmic bytes exceed this: every line of them is read once per
+// product, and a product that large finds nothing of them in the caches anyway.  Not below it: a matrix that the L2s or the
+// Infinity Cache hold, wholly or in good part, is slower with the hint (profiles/col16_lane_order_measured.txt has the curve).
+constexpr double kReadOnceMinBytes = 1024.0 * 1024 * 1024;
 
 int build_tile_plan_parts(smvp_csr *h)
 {
@@ -522,7 +535,11 @@ int build_tile_plan_parts(smvp_csr *h)
     // plan option: 0 = every product sweeps forward, 1 = the plain launches alternate whatever the size; default: they alternate
     // where one product's bytes do not fit the Infinity Cache anyway (see kSweepAlternateMinBytes)
     const int alternate = smvp::option("csr_sweep_alternate", -1);
-    t.sweep_alternate = alternate < 0 ? 12.0 * (double)h->nnz + 12.0 * h->rows + 8.0 * h->cols > kSweepAlternateMinBytes : alternate != 0;
+    const double product_bytes = 12.0 * (double)h->nnz + 12.0 * h->rows + 8.0 * h->cols;
+    t.sweep_alternate = alternate < 0 ? product_bytes > kSweepAlternateMinBytes : alternate != 0;
+    // plan option: 0 / 1 = the single launches' val and col16 loads never / always carry the read-once hint; default: by size
+    const int read_once = smvp::option("csr_read_once", -1);
+    t.read_once = h->flavor != smvp::kFlavorCsr ? 0 : read_once < 0 ? product_bytes > kReadOnceMinBytes : read_once != 0;
     if (tile_ordered(h->flavor)) {
         // every tile's entries in TJDS order + what each tile reads past its end, in row order
         std::vector<int> ovf_ptr((size_t)ntiles + 1, 0);
@@ -859,8 +876,11 @@ extern "C" int smvp_csr_gather_spread(smvp_csr_t *h, double *spread)
     return SMVP_OK;
 }
 
-static void fill_owner_launch(const smvp_csr_t *h, const double *d_x, double *d_y, unsigned long long *stamps, smvp::OwnerLaunch *out)
+static int fill_owner_launch(const smvp_csr_t *h, const double *d_x, double *d_y, unsigned long long *stamps, smvp::OwnerLaunch *out)
 {
+    if (h->tile.d_col16 && h->tile.col16_tile != smvp::kStreamBlock * h->vpt)  // (every re-plan rebuilds them: a plan bug, not a caller's)
+        return smvp::fail(SMVP_ERR_INVALID, "the 16-bit column offsets were laid out for %d-entry tiles, the launch has %d-entry tiles",
+                          h->tile.col16_tile, smvp::kStreamBlock * h->vpt);
     smvp::OwnerLaunch &l = *out;
     l.row_ptr = h->d_row_ptr, l.col_ind = h->d_col_ind, l.val = h->d_val, l.x = d_x, l.y = d_y;
     l.tile_row = h->tile.d_tile_row, l.tile_next = h->tile.d_tile_next;
@@ -875,7 +895,9 @@ static void fill_owner_launch(const smvp_csr_t *h, const double *d_x, double *d_
     l.rows = h->rows, l.nnz = h->nnz, l.ntiles = h->tile.ntiles;
     l.col16 = h->tile.d_col16, l.col_base = h->tile.d_col_base;
     l.row_rel = h->tile.d_row_rel;
+    l.read_once = h->tile.read_once;
     l.unit_x = h->src.unit_operand ? 1 : 0;
+    return SMVP_OK;
 }
 
 // `reps` products of the tile kernel in ONE launch, each product's window stamped (csr_stream_owner_repeat); grid from
@@ -893,7 +915,8 @@ int smvp::csr_spmv_repeat(smvp_csr_t *h, const double *d_x, double *d_y, void *s
 {
     DeviceScope on(h->device);
     smvp::OwnerLaunch l{};
-    fill_owner_launch(h, d_x, d_y, stamps, &l);
+    if (int rc = fill_owner_launch(h, d_x, d_y, stamps, &l))
+        return rc;
     const hipError_t e = smvp::launch_csr_stream_owner_repeat(h->vpt, owner_flavor(h), l, reps, grid, ctl_words,
                                                               first_of_run, patience, (hipStream_t)stream);
     if (e != hipSuccess)
@@ -966,7 +989,8 @@ int smvp::csr_spmv_stamped(smvp_csr_t *h, const double *d_x, double *d_y, void *
         e = smvp::launch_csr_vector(h->lanes_per_row, h->d_row_ptr, h->d_col_ind, h->d_val, d_x, d_y, h->rows, st);
     else if (h->kernel == SMVP_CSR_KERNEL_STREAM) {
         smvp::OwnerLaunch l{};
-        fill_owner_launch(h, d_x, d_y, stamps, &l);
+        if (int rc = fill_owner_launch(h, d_x, d_y, stamps, &l))
+            return rc;
         // the plain single launch, stamped or not, of a CSR handle, of a binned plan's near handle and of a TJDS handle's
         // tile-ordered stream (all come through here): this one sweeps the way the last one did not
         l.backward = h->tile.sweep_backward;

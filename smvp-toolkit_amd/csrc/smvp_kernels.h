@@ -94,6 +94,7 @@ struct OwnerLaunch {
     const int *run_ptr = nullptr, *run_tab = nullptr;
     const unsigned short *row_rel = nullptr;   // rows' first entries relative to their tile's (or nullptr: row_ptr is read)
     int rows = 0, nnz = 0, ntiles = 0;
+    int read_once = 0;  // plain launches of the CSR flavours at 1024- / 2048-entry tiles: the kernel form whose val (and 16-byte col16) loads carry the read-once hint
     int backward = 0;   // plain launches: sweep the tiles from the last to the first (tile_of_block_swept; the repeating launch ignores it)
 };
 hipError_t launch_csr_stream_owner(int vpt, int flavor, const OwnerLaunch &l, hipStream_t stream);

@@ -215,6 +215,9 @@ __global__ __launch_bounds__(kStreamBlock) void csr_stream_tiles(
 // not bound by the L1's address path.  The lane-strided alternative (entry 64 k + l; 8-byte and 2-byte loads) was built and
 // measured too: 115.3 M accesses, two thirds more load instructions, headline -1.2 %, pwt x459 +2.7 % -- not merged.
 // prod[] holds every product at its row-major place whatever the layout, so phase 2 and every sum's order are untouched.
+// Since then, at 2048-entry tiles, Csr16's offsets lie in the plan in the order the lanes hold them (smvp::col16_slot): one
+// 16-byte load per lane instead of four 4-byte words, and products larger than the caches run the read_once:: form of the kernel
+// below (profiles/col16_lane_order_measured.txt: memplus x944 0.2616 -> 0.2507 ms, pwt x459 -7.7 %).
 //
 // FLAVOR selects what an "entry" is (owner_entry below):
 //   kFlavorCsr     CSR: value val[j], operand x[col_ind[j]]                       (main-cli.c:410-416)
@@ -242,6 +245,7 @@ __global__ __launch_bounds__(kStreamBlock) void csr_stream_tiles(
 // ---------------------------------------------------------------------------
 typedef int int4v __attribute__((ext_vector_type(4)));               // clang vectors: what the non-temporal builtins take
 typedef int int2v __attribute__((ext_vector_type(2)));
+typedef double double2v __attribute__((ext_vector_type(2)));
 
 // The streams every flavour reads are plain __restrict__ kernel parameters (the compiler then keeps the uniform plan
 // reads on the scalar unit and is free to order the loads); what only some flavours need travels in this struct.
@@ -352,7 +356,8 @@ __device__ unsigned long long g_owner_phase[8];
 
 // The body of the owner kernel for workgroup number `block` of the launch's grid (the plain kernel passes blockIdx.x; the
 // repeating kernel below walks the same grid several times).  Every thread of the workgroup leaves through the same exit.
-template <int VPT, int FLAVOR, bool STAMPED>
+// STREAMED: the full tiles' val loads (CSR flavours, VPT 4 and 8) and Csr16's 16-byte offset loads carry the read-once hint.
+template <int VPT, int FLAVOR, bool STAMPED, bool STREAMED = false>
 __device__ __forceinline__ void owner_body(
     const int *__restrict__ row_ptr, const int *__restrict__ col_ind, const double *__restrict__ val,
     const double *__restrict__ x, double *__restrict__ y, const int *__restrict__ tile_row,
@@ -476,10 +481,25 @@ __device__ __forceinline__ void owner_body(
             if constexpr (COL16) {
                 const int base = ex.col_base[b];
                 if (base >= 0) {
+                    if constexpr (VPT == 8) {
+                        // the plan keeps the offsets of a narrow 2048-entry tile in the order the lanes hold the entries
+                        // (smvp::col16_slot): this lane's 8 offsets are one 16-byte load, and a wave instruction covers 1 KiB once
+                        const unsigned short *mine = ex.col16 + s + ((t >> 6) * (64 * VPT) + (t & 63) * VPT + lane_salt);
+                        unsigned w[VPT / 2];
+                        if constexpr (STREAMED)
+                            *reinterpret_cast<int4v *>(w) = __builtin_nontemporal_load(reinterpret_cast<const int4v *>(mine));
+                        else
+                            *reinterpret_cast<int4v *>(w) = *reinterpret_cast<const int4v *>(mine);
 #pragma unroll
-                    for (int k = 0; k < VPT; k += 2) {  // two 16-bit offsets per 4-byte load
-                        const unsigned w = *reinterpret_cast<const unsigned *>(ex.col16 + s + lane_entry(k));
-                        c[k] = base + (int)(w & 0xffffu), c[k + 1] = base + (int)(w >> 16);
+                        for (int k = 0; k < VPT; k += 2)
+                            c[k] = base + (int)(w[k / 2] & 0xffffu), c[k + 1] = base + (int)(w[k / 2] >> 16);
+                    } else {
+                        // 1024-entry tiles keep the plain order (one 8-byte load per lane measured 1.5-3 % slower than these two)
+#pragma unroll
+                        for (int k = 0; k < VPT; k += 2) {  // two 16-bit offsets per 4-byte load
+                            const unsigned w = *reinterpret_cast<const unsigned *>(ex.col16 + s + lane_entry(k));
+                            c[k] = base + (int)(w & 0xffffu), c[k + 1] = base + (int)(w >> 16);
+                        }
                     }
                 } else {  // a tile whose columns span 65536 or more
                     load_cols();
@@ -494,8 +514,12 @@ __device__ __forceinline__ void owner_body(
             }
             if constexpr (CSR) {
 #pragma unroll
-                for (int k = 0; k < VPT; k += 2)
-                    *reinterpret_cast<double2 *>(&v[k]) = *reinterpret_cast<const double2 *>(a.val + s + lane_entry(k));
+                for (int k = 0; k < VPT; k += 2) {  // (each instruction covers 1 KiB of val exactly once)
+                    if constexpr (STREAMED)
+                        *reinterpret_cast<double2v *>(&v[k]) = __builtin_nontemporal_load(reinterpret_cast<const double2v *>(a.val + s + lane_entry(k)));
+                    else
+                        *reinterpret_cast<double2 *>(&v[k]) = *reinterpret_cast<const double2 *>(a.val + s + lane_entry(k));
+                }
             }
         } else {  // VPT == 1: 256-entry tiles for matrices too small to fill the chip with 1024-entry ones
             c[0] = a.col_ind[j0];
@@ -795,6 +819,25 @@ __global__ __launch_bounds__(kStreamBlock) void csr_stream_owner(
     owner_body<VPT, FLAVOR, STAMPED>(row_ptr, col_ind, val, x, y, tile_row, tile_next, rows, nnz_arg, ntiles, tile_group_arg, ex,
                                      (int)blockIdx.x);
 }
+
+// The same kernel with the read-once hint on its value and offset streams (owner_body's STREAMED), for the plain CSR launches
+// of a plan that asks for it (OwnerLaunch::read_once: a product larger than the caches, see the engine's kReadOnceMinBytes).
+// A second kernel and not a uniform word of the launch: with the hint behind a uniform branch, the compiler first merged the
+// two loads into one without it, and once they were kept apart (other vector types) the hinted path ran 15 % SLOWER than
+// without the hint (memplus x944 0.2930 ms against 0.2552) where this form runs 3 % faster
+// (profiles/col16_lane_order_measured.txt).  In a namespace of its own so that its name in a profile is still
+// csr_stream_owner<VPT, FLAVOR, STAMPED>, which is what describe() says and the tools look for.
+namespace read_once {
+template <int VPT, int FLAVOR, bool STAMPED>
+__global__ __launch_bounds__(kStreamBlock) void csr_stream_owner(
+    const int *__restrict__ row_ptr, const int *__restrict__ col_ind, const double *__restrict__ val,
+    const double *__restrict__ x, double *__restrict__ y, const int *__restrict__ tile_row,
+    const int *__restrict__ tile_next, int rows, int nnz_arg, int ntiles, int tile_group_arg, const OwnerExtra ex)
+{
+    owner_body<VPT, FLAVOR, STAMPED, true>(row_ptr, col_ind, val, x, y, tile_row, tile_next, rows, nnz_arg, ntiles, tile_group_arg, ex,
+                                           (int)blockIdx.x);
+}
+}  // namespace read_once
 
 #ifndef SMVP_TU_ILP
 // ---------------------------------------------------------------------------
@@ -1439,22 +1482,28 @@ hipError_t launch_owner_csr_ilp(int vpt, int flavor, const OwnerLaunch &l, const
 {
     const OwnerExtra &ex = *static_cast<const OwnerExtra *>(extra);
     const dim3 grid(grid_x);
-#define SMVP_OWNER_ST(V, F, S)                                                                                     \
-    hipLaunchKernelGGL((csr_stream_owner<V, F, S>), grid, dim3(kStreamBlock), 0, stream, l.row_ptr, l.col_ind, l.val, \
+#define SMVP_OWNER_ST(K, V, F, S)                                                                                  \
+    hipLaunchKernelGGL((K<V, F, S>), grid, dim3(kStreamBlock), 0, stream, l.row_ptr, l.col_ind, l.val, \
                        l.x, l.y, l.tile_row, l.tile_next, l.rows, l.nnz, l.ntiles, group, ex)
-#define SMVP_OWNER(V, F)                  \
+#define SMVP_OWNER(K, V, F)               \
     if (vpt == V && flavor == F) {        \
         if (l.stamps)                     \
-            SMVP_OWNER_ST(V, F, true);    \
+            SMVP_OWNER_ST(K, V, F, true); \
         else                              \
-            SMVP_OWNER_ST(V, F, false);   \
+            SMVP_OWNER_ST(K, V, F, false);\
         return hipGetLastError();         \
     }
-    SMVP_OWNER(1, kFlavorCsr)
-    SMVP_OWNER(4, kFlavorCsr)
-    SMVP_OWNER(8, kFlavorCsr)
-    SMVP_OWNER(4, kFlavorCsr16)
-    SMVP_OWNER(8, kFlavorCsr16)
+    if (l.read_once) {  // (the 256-entry tiles have no such form and take the plain one)
+        SMVP_OWNER(read_once::csr_stream_owner, 4, kFlavorCsr)
+        SMVP_OWNER(read_once::csr_stream_owner, 8, kFlavorCsr)
+        SMVP_OWNER(read_once::csr_stream_owner, 4, kFlavorCsr16)
+        SMVP_OWNER(read_once::csr_stream_owner, 8, kFlavorCsr16)
+    }
+    SMVP_OWNER(csr_stream_owner, 1, kFlavorCsr)
+    SMVP_OWNER(csr_stream_owner, 4, kFlavorCsr)
+    SMVP_OWNER(csr_stream_owner, 8, kFlavorCsr)
+    SMVP_OWNER(csr_stream_owner, 4, kFlavorCsr16)
+    SMVP_OWNER(csr_stream_owner, 8, kFlavorCsr16)
 #undef SMVP_OWNER
 #undef SMVP_OWNER_ST
     return hipErrorInvalidValue;

@@ -40,4 +40,25 @@ SMVP_HOST_DEVICE inline __attribute__((always_inline)) int tile_of_block_swept(i
     return tile_of_block(back_grid ? back_grid - 1 - block : block, group);
 }
 
+// Phase 1 of the tile kernel, row-ordered flavours, tiles of 256 * vpt entries (vpt 4 or 8): the offset in the tile of entry k
+// (0 ... vpt - 1) of thread t.  A wavefront takes 64 * vpt consecutive entries in slabs of 128; of every slab lane l has the
+// two entries 2 l and 2 l + 1 (owner_body's lane_entry).
+SMVP_HOST_DEVICE inline __attribute__((always_inline)) int tile_lane_entry(int t, int k, int vpt)
+{
+    return (t >> 6) * (64 * vpt) + 2 * (t & 63) + 128 * (k >> 1) + (k & 1);
+}
+
+// Where the plan keeps the 16-bit column offset of the entry at offset o of a full, narrow tile (column_offsets writes it there,
+// owner_body reads it from there): in the order the lanes hold the entries, so that the vpt offsets of a lane are one load.
+// The inverse of tile_lane_entry: col16_slot(tile_lane_entry(t, k, vpt), vpt) = (t >> 6) * 64 * vpt + (t & 63) * vpt + k.
+// A permutation inside every wavefront's chunk of 64 * vpt entries, hence inside the tile.
+// The library lays out the 2048-entry tiles this way (vpt 8); the formula holds for vpt 4 as well.
+constexpr int kCol16LaneOrderTile = 2048;
+SMVP_HOST_DEVICE inline __attribute__((always_inline)) int col16_slot(int o, int vpt)
+{
+    const int chunk = 64 * vpt;
+    const int w = o / chunk, q = o % chunk, l = (q % 128) / 2, k = 2 * (q / 128) + (q & 1);
+    return w * chunk + l * vpt + k;
+}
+
 }  // namespace smvp

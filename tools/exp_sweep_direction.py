@@ -17,7 +17,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "smvp-toolkit_amd", "python")); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
 
-OPTION = "csr_sweep_alternate"
+OPTION = "csr_sweep_alternate"   # (--option names another 0 / 1 plan option of the tile kernel, e.g. csr_read_once)
 
 
 def main():
@@ -26,7 +26,9 @@ def main():
     ap.add_argument("--alternations", type=int, default=3); ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--steps", type=int, default=100); ap.add_argument("--prewarm", type=int, default=150)
     ap.add_argument("--on", default="default", choices=["default", "1"], help='the "on" column: the library\'s default (alternate where one product exceeds the Infinity Cache) or 1 (alternate whatever the size)')
+    ap.add_argument("--option", default=OPTION, help="the plan option the two columns differ in")
     a = ap.parse_args()
+    globals()["OPTION"] = a.option
     import torch, smvp_toolkit_amd as sm
     from smvp_toolkit_amd import sharding
     import bench_core as core
