@@ -615,8 +615,9 @@ int smvp_vector_dot(int device, int n, const double *d_a, const double *d_b, dou
  * d_x do not depend on check_every (which decides how many products are enqueued in vain, and how often the host waits).  This is
  * stronger than the power method's "the reason belongs to the looked step": a converged x is never iterated past.
  * Symmetry and definiteness are the caller's contract and are not checked; SMVP_CG_BREAKDOWN is what a matrix that is visibly
- * not positive definite gets (smvp_csr_bicgstab below is for a general matrix).  A diagonal preconditioner: smvp_csr_pcg below.  The
- * sharded handles are out of scope. */
+ * not positive definite gets (smvp_csr_bicgstab below is for a general matrix).  A diagonal preconditioner: smvp_csr_pcg below.
+ * k right-hand sides in one call, sharing every read of the matrix: smvp_csr_cg_multi (K20) below.  The sharded handles are out of
+ * scope. */
 enum { SMVP_CG_CONVERGED = 0, SMVP_CG_MAX_STEPS = 1, SMVP_CG_BREAKDOWN = 2, SMVP_CG_NONFINITE = 3 };
 typedef struct smvp_cg_opts {
     unsigned struct_size; /* set by smvp_cg_opts_default, checked as for smvp_run_opts_t */
@@ -704,7 +705,8 @@ int smvp_tjds_diagonal(const smvp_tjds_t *h, double *d_diag, void *stream);
  * k % check_every == 0, and k == max_steps -- and only to leave the loop: steps, updates, reason, the three histories and every bit
  * of d_x do not depend on check_every.  A preconditioner made of two triangular solves (symmetric Gauss-Seidel, an incomplete
  * factorisation: the caller's, or K17's ILU(0)) is smvp_csr_pcg_tri, K16, below.  Preconditioned BiCGSTAB is smvp_csr_pbicgstab, K18,
- * further below; the sharded handles are out of scope. */
+ * further below.  k right-hand sides under one d_m in one call: smvp_csr_cg_multi (K20), below.  The sharded handles are out of
+ * scope. */
 typedef struct smvp_pcg_result {
     int steps;   /* products of a direction done (the one for r_0 is not counted) */
     int updates; /* updates of x done: steps, or steps - 1 after rule A */
@@ -736,6 +738,63 @@ int smvp_csr_pcg(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, c
                  smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each, void *stream);
 int smvp_tjds_pcg(smvp_tjds_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x, const double *d_m,
                   smvp_pcg_result_t *result, double *rr_each, double *rz_each, double *sigma_each, void *stream);
+
+/* ------------------------------------------------- conjugate gradients for k right-hand sides */
+/* k independent conjugate-gradient runs on one square n x n handle that share every read of the matrix and every launch, kernel
+ * K20: the loop around the block products smvp_csr_spmm (K7) and smvp_tjds_spmm (K10).  It is NOT block CG: the columns share no
+ * Krylov space, so every number of a column still has one right answer.  One entry point covers plain CG (d_m == NULL: K12's rules)
+ * and a diagonal preconditioner (d_m given: K14's rules; n doubles shared by all columns).
+ *
+ * Operands.  B, X0 and X are n x k row-major device blocks with leading dimensions of their own, each >= k: smvp_csr_spmm's
+ * conventions -- a contiguous (n, k) array, or a column slice of a wider one.  Element (i, v) of B lies at d_B[i * ldb + v].  Padding
+ * columns of X are never written.  d_X0 == NULL is zeros (ldx0 is then ignored).  d_X may be d_X0 with ldx == ldx0; any other
+ * overlap of the byte ranges of d_X0 and d_X, and any overlap of d_X with d_B or d_m, is SMVP_ERR_INVALID.  d_B, d_X0 and d_m are
+ * only read.  After SMVP_ERR_HIP the content of d_X is unspecified.
+ *
+ * Bits.  Column v of every output is the run this header already defines: with d_m == NULL the smvp_csr_cg run on b = B(:, v),
+ * x_0 = X0(:, v), with d_m given the smvp_csr_pcg run on the same operands -- the same dot, the same order of additions, the same
+ * rules in the same order, every rule evaluated on the device at every step -- with ONE difference: q_k is column v of
+ * smvp_csr_spmm / smvp_tjds_spmm on the k directions, i.e. the serial loop over the row for CSR and the row's entries in ascending
+ * TJDS position for TJDS.  It does not depend on the handle's SpMV plan or TJDS mode.  No number of column v depends on k, on v, on
+ * the other columns' contents (a NaN column included), on any leading dimension, on check_every or on the stream.  Where the
+ * handle's single product is itself the serial loop on every row -- the default kernel on rows of at most 32 entries, see
+ * smvp_csr_spmm's "Bits" -- every number equals the one-vector call's, bit for bit.
+ *
+ * Columns stop on their own.  Each column has its own status block and its own steps / updates / reason.  Once a column's rule has
+ * fired nothing is written to that column of X or to its histories.  The host loop ends when all columns have stopped; until then
+ * a stopped column is still multiplied (in vain) by the block product, which cannot disturb the others because the block product's
+ * columns are independent.  Stopped columns are not compacted away.
+ *   - results: a HOST array of k blocks; results[v] is column v's smvp_pcg_result_t as smvp_csr_pcg fills it.  With d_m == NULL
+ *     rz = rr.
+ *   - rr_each, rz_each: caller-owned HOST arrays of k * (max_steps + 1) doubles; column v's history is contiguous at
+ *     [v * (max_steps + 1) + j], filled j = 0 .. updates_v.  sigma_each: k * max_steps doubles, column v at [v * max_steps + j],
+ *     filled j = 0 .. steps_v - 1.  Everything beyond the filled elements is left untouched.  Any of the three may be NULL, and
+ *     rz_each is left untouched when d_m is NULL.  They come from device-side histories copied back once at the end.
+ *   - The host reads the k status blocks at looked steps only -- step 0, every step that is a multiple of check_every, and
+ *     max_steps -- and only to leave the loop.
+ *   - The call returns after the work on `stream` has finished.  It allocates its workspace per call -- R, P and Q (n x k, ld = k),
+ *     the partials of three dots per column (at most 2048 each), a few words per column, the histories, 2 x k status blocks -- and
+ *     frees it on every way out.  Beside the block product (one launch per 16 columns) a step is two launches of one workgroup per
+ *     column and three passes per group of at most 16 columns: 10 k passes over a vector (12 k with d_m), as k runs of K12 / K14.
+ *   - SMVP_ERR_INVALID for everything smvp_csr_cg / smvp_csr_pcg refuse (a NULL d_m excepted: it selects plain CG), and for: k < 1;
+ *     a leading dimension below k; a NULL results; a capturing stream.  Nothing is enqueued then, d_X and results are left
+ *     untouched, and a capturing stream's capture stays valid.
+ *   - SMVP_ERR_UNSUPPORTED (likewise) for a CSR handle that is not plain CSR.  A TJDS handle is accepted in EVERY mode, ATOMIC and
+ *     ref-quirks included: smvp_tjds_spmm's bits depend on neither.
+ *   - n == 0: SMVP_OK, and every results[v] has steps 0, updates 0, reason SMVP_CG_CONVERGED, rr = rz = bb = +0.0.
+ *   - State: a CSR handle's SpMV plan is untouched -- smvp_csr_spmv after the call gives the bits it gave before.  The first call
+ *     builds the handle's block-product plan if it has none, as the first smvp_csr_spmm / smvp_tjds_spmm would (4 bytes per row; for
+ *     TJDS 8 bytes per entry and 8 per row), and keeps it.  A TJDS handle's permuted operand and forward state are untouched, as
+ *     smvp_tjds_spmm promises: unlike after smvp_tjds_cg, a smvp_tjds_spmv after the call needs no new smvp_tjds_set_x.  `val` is
+ *     read in place: adopted values changed in place are seen by the next call.
+ * Out of scope: true block CG, compaction of stopped columns, the triangular-solve preconditioners of K16 (K15 has no solve for k
+ * vectors), BiCGSTAB and GMRES for k right-hand sides, the sharded handles, column-major operands. */
+int smvp_csr_cg_multi(smvp_csr_t *h, const smvp_cg_opts_t *opts, int k, const double *d_B, long long ldb, const double *d_X0,
+                      long long ldx0, double *d_X, long long ldx, const double *d_m, smvp_pcg_result_t *results, double *rr_each,
+                      double *rz_each, double *sigma_each, void *stream);
+int smvp_tjds_cg_multi(smvp_tjds_t *h, const smvp_cg_opts_t *opts, int k, const double *d_B, long long ldb, const double *d_X0,
+                       long long ldx0, double *d_X, long long ldx, const double *d_m, smvp_pcg_result_t *results, double *rr_each,
+                       double *rz_each, double *sigma_each, void *stream);
 
 /* ------------------------------------------------- sparse triangular solves */
 /* T x = b where T is a triangle of a square plain-CSR handle's matrix AS STORED, kernel K15 (new: the reference only multiplies).
@@ -848,7 +907,8 @@ int smvp_csr_trsv_levels(int rows, const int *row_ptr, const int *col_ind, int u
  *   - State: the handle as after smvp_csr_pcg / smvp_tjds_pcg.  The plans are used on `stream` for the duration of the call (a
  *     plan is used by one stream at a time, as ever) and are unchanged afterwards, as are the handles they borrow: smvp_trsv_solve
  *     gives the bits it gave before.  `val` of either handle changed in place is seen by the next call.
- * Out of scope: omega inside the library, the sharded handles, a block of k right-hand sides.  BiCGSTAB preconditioned by the same
+ * Out of scope: omega inside the library, the sharded handles, a block of k right-hand sides (smvp_csr_cg_multi, K20, takes a
+ * diagonal preconditioner only: K15 has no solve for k vectors).  BiCGSTAB preconditioned by the same
  * M, for a matrix that is not symmetric, is smvp_csr_pbicgstab, K18, below. */
 int smvp_csr_pcg_tri(smvp_csr_t *h, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                      smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_pcg_result_t *result, double *rr_each,

@@ -84,12 +84,12 @@ inline int refuse_capture(hipStream_t st, const char *why)
 }
 
 // Do the byte ranges of two operands meet?  An operand is n rows of k doubles, ld doubles from one row to the next (a vector:
-// ld = 1, k = 1); without rows it has no bytes.
-inline bool operands_overlap(const double *a, long long lda, int na, const double *b, long long ldb, int nb, int k)
+// ld = 1, k = 1); without rows it has no bytes.  kb: the columns of b where they are not a's (a vector against a block).
+inline bool operands_overlap(const double *a, long long lda, int na, const double *b, long long ldb, int nb, int k, int kb = 0)
 {
     const unsigned __int128 a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     const unsigned __int128 a1 = a0 + (na > 0 ? ((unsigned __int128)(na - 1) * (unsigned long long)lda + (unsigned)k) * 8u : 0);
-    const unsigned __int128 b1 = b0 + (nb > 0 ? ((unsigned __int128)(nb - 1) * (unsigned long long)ldb + (unsigned)k) * 8u : 0);
+    const unsigned __int128 b1 = b0 + (nb > 0 ? ((unsigned __int128)(nb - 1) * (unsigned long long)ldb + (unsigned)(kb ? kb : k)) * 8u : 0);
     return a && b && na > 0 && nb > 0 && a0 < b1 && b0 < a1;
 }
 
@@ -213,6 +213,16 @@ int cg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t 
            void *stream, const HandleProduct &product);
 int cg_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
            smvp_cg_result_t *result, double *rr_each, double *sigma_each, void *stream, const HandleProduct &product);
+
+// conjugate gradients for k right-hand sides (K20, smvp_cg_multi.hip): k runs of K12 (d_m == NULL) or K14 that share every launch.
+// The product is a block product of the handle (BlockProduct): Y = A X for the call's k columns, X and Y row-major device blocks with
+// leading dimensions of their own, enqueued on the call's stream -- smvp_csr_spmm's / smvp_tjds_spmm's enqueue, which builds the
+// handle's block-product plan where it has none.
+using BlockProduct = std::function<int(const double *d_X, long long ldx, double *d_Y, long long ldy)>;
+int cg_multi_check_args(const char *fn, const void *h, const smvp_cg_opts_t *opts, const void *results, const double *d_B);
+int cg_multi_run(const char *fn, int device, int rows, int cols, const smvp_cg_opts_t *opts, int k, const double *d_B, long long ldb,
+                 const double *d_X0, long long ldx0, double *d_X, long long ldx, const double *d_m, smvp_pcg_result_t *results,
+                 double *rr_each, double *rz_each, double *sigma_each, void *stream, const BlockProduct &product);
 
 // BiCGSTAB, two products a step.  M == nullptr: K13; else K18 with phat = M^-1 p and shat = M^-1 s, which pbicgstab_check_args
 // refuses where all three parts are NULL.

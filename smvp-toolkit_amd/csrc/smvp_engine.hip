@@ -1230,17 +1230,10 @@ extern "C" int smvp_csr_plan_info(const smvp_csr_t *h, smvp_plan_info_t *out)
     return SMVP_OK;
 }
 
-// K7: every argument is checked before anything is enqueued; the first call builds the plan (and synchronises `stream`)
-extern "C" int smvp_csr_spmm(smvp_csr_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream)
+// K7's enqueue, for smvp_csr_spmm and for K20's steps: the arguments are checked and the handle's device is current.  The first call
+// on a handle builds the plan (and synchronises `st`).
+static int csr_spmm_enqueue(smvp_csr_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, hipStream_t st)
 {
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: null handle");
-    if (h->flavor != smvp::kFlavorCsr)
-        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_spmm: plain CSR handles only (this one belongs to a TJDS matrix)");
-    if (int rc = check_block_operands("smvp_csr_spmm", k, d_X, ldx, h->cols, d_Y, ldy, h->rows, h->nnz))  // X(c, v), c < cols; Y(r, v), r < rows
-        return rc;
-    DeviceScope on(h->device);
-    hipStream_t st = (hipStream_t)stream;
     if (!h->spmm.planned) {
         if (int rc = refuse_capture(st, "smvp_csr_spmm: the first call on a handle builds its plan and cannot be captured "
                                         "(call it once outside the capture)"))
@@ -1259,6 +1252,34 @@ extern "C" int smvp_csr_spmm(smvp_csr_t *h, int k, const double *d_X, long long 
     if (e != hipSuccess)
         return smvp::fail(SMVP_ERR_HIP, "smvp_csr_spmm: launch failed: %s", hipGetErrorString(e));
     return SMVP_OK;
+}
+
+// K7: every argument is checked before anything is enqueued; the first call builds the plan (and synchronises `stream`)
+extern "C" int smvp_csr_spmm(smvp_csr_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_spmm: null handle");
+    if (h->flavor != smvp::kFlavorCsr)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_spmm: plain CSR handles only (this one belongs to a TJDS matrix)");
+    if (int rc = check_block_operands("smvp_csr_spmm", k, d_X, ldx, h->cols, d_Y, ldy, h->rows, h->nnz))  // X(c, v), c < cols; Y(r, v), r < rows
+        return rc;
+    DeviceScope on(h->device);
+    return csr_spmm_enqueue(h, k, d_X, ldx, d_Y, ldy, (hipStream_t)stream);
+}
+
+// K20: k runs of K12 (d_m == NULL) or K14 around K7's enqueue on all k directions; the SpMV plan is neither used nor touched
+extern "C" int smvp_csr_cg_multi(smvp_csr_t *h, const smvp_cg_opts_t *opts, int k, const double *d_B, long long ldb, const double *d_X0,
+                                 long long ldx0, double *d_X, long long ldx, const double *d_m, smvp_pcg_result_t *results, double *rr_each,
+                                 double *rz_each, double *sigma_each, void *stream)
+{
+    if (int rc = smvp::cg_multi_check_args("smvp_csr_cg_multi", h, opts, results, d_B))
+        return rc;
+    if (int rc = refuse_tjds_flavor("smvp_csr_cg_multi", h))
+        return rc;
+    return smvp::cg_multi_run("smvp_csr_cg_multi", h->device, h->rows, h->cols, opts, k, d_B, ldb, d_X0, ldx0, d_X, ldx, d_m, results, rr_each,
+                              rz_each, sigma_each, stream, [h, k, stream](const double *X, long long ldX, double *Y, long long ldY) {
+                                  return csr_spmm_enqueue(h, k, X, ldX, Y, ldY, (hipStream_t)stream);
+                              });
 }
 
 extern "C" int smvp_csr_spmm_describe(const smvp_csr_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes, smvp_plan_info_t *plan)

@@ -597,17 +597,10 @@ extern "C" int smvp_tjds_spmm_transposed_describe(const smvp_tjds_t *h, int k, c
     return SMVP_OK;
 }
 
-// K10: Y = A X for k vectors from the handle's own arrays (the true start_pos, not the ref-quirks edit) through a plan of its own
-// and the caller's X: no x_perm, no mode's plan, no value cache is read or written.  Every argument is checked before anything
-// is enqueued; the first call builds the plan (and synchronises `stream`).
-extern "C" int smvp_tjds_spmm(smvp_tjds_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream)
+// K10's enqueue, for smvp_tjds_spmm and for K20's steps: the arguments are checked and the handle's device is current.  The first
+// call on a handle builds the plan (and synchronises `st`).
+static int tjds_spmm_enqueue(smvp_tjds_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, hipStream_t st)
 {
-    if (!h)
-        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: null handle");
-    if (int rc = check_block_operands("smvp_tjds_spmm", k, d_X, ldx, h->cols, d_Y, ldy, h->rows, h->nnz))  // X(c, v), c < cols; Y(r, v), r < rows
-        return rc;
-    DeviceScope on(h->device);
-    hipStream_t st = (hipStream_t)stream;
     TjdsSpmmPlan &p = h->spmm;
     if (!p.planned) {
         if (int rc = refuse_capture(st, "smvp_tjds_spmm: the first call on a handle builds its plan and cannot be captured "
@@ -630,6 +623,33 @@ extern "C" int smvp_tjds_spmm(smvp_tjds_t *h, int k, const double *d_X, long lon
     if (e != hipSuccess)
         return smvp::fail(SMVP_ERR_HIP, "smvp_tjds_spmm: launch failed: %s", hipGetErrorString(e));
     return SMVP_OK;
+}
+
+// K10: Y = A X for k vectors from the handle's own arrays (the true start_pos, not the ref-quirks edit) through a plan of its own
+// and the caller's X: no x_perm, no mode's plan, no value cache is read or written.  Every argument is checked before anything
+// is enqueued; the first call builds the plan (and synchronises `stream`).
+extern "C" int smvp_tjds_spmm(smvp_tjds_t *h, int k, const double *d_X, long long ldx, double *d_Y, long long ldy, void *stream)
+{
+    if (!h)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_tjds_spmm: null handle");
+    if (int rc = check_block_operands("smvp_tjds_spmm", k, d_X, ldx, h->cols, d_Y, ldy, h->rows, h->nnz))  // X(c, v), c < cols; Y(r, v), r < rows
+        return rc;
+    DeviceScope on(h->device);
+    return tjds_spmm_enqueue(h, k, d_X, ldx, d_Y, ldy, (hipStream_t)stream);
+}
+
+// K20: k runs of K12 (d_m == NULL) or K14 around K10's enqueue on all k directions.  K10's bits depend neither on the mode nor on
+// ref-quirks, so every handle is accepted; x_perm and the forward product's state are neither read nor written.
+extern "C" int smvp_tjds_cg_multi(smvp_tjds_t *h, const smvp_cg_opts_t *opts, int k, const double *d_B, long long ldb, const double *d_X0,
+                                  long long ldx0, double *d_X, long long ldx, const double *d_m, smvp_pcg_result_t *results,
+                                  double *rr_each, double *rz_each, double *sigma_each, void *stream)
+{
+    if (int rc = smvp::cg_multi_check_args("smvp_tjds_cg_multi", h, opts, results, d_B))
+        return rc;
+    return smvp::cg_multi_run("smvp_tjds_cg_multi", h->device, h->rows, h->cols, opts, k, d_B, ldb, d_X0, ldx0, d_X, ldx, d_m, results, rr_each,
+                              rz_each, sigma_each, stream, [h, k, stream](const double *X, long long ldX, double *Y, long long ldY) {
+                                  return tjds_spmm_enqueue(h, k, X, ldX, Y, ldY, (hipStream_t)stream);
+                              });
 }
 
 extern "C" int smvp_tjds_spmm_describe(const smvp_tjds_t *h, int k, char *kernel_name, size_t cap, double *alg_bytes, smvp_plan_info_t *plan)

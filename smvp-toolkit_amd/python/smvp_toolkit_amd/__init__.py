@@ -178,7 +178,7 @@ EXPORTS = [
     "smvp_tjds_spmm_transposed", "smvp_tjds_spmm_transposed_describe", "smvp_tjds_spmm", "smvp_tjds_spmm_describe",
     "smvp_power_opts_default", "smvp_csr_power_method", "smvp_tjds_power_method",
     "smvp_vector_dot", "smvp_cg_opts_default", "smvp_csr_cg", "smvp_tjds_cg",
-    "smvp_csr_diagonal", "smvp_tjds_diagonal", "smvp_csr_pcg", "smvp_tjds_pcg",
+    "smvp_csr_diagonal", "smvp_tjds_diagonal", "smvp_csr_pcg", "smvp_tjds_pcg", "smvp_csr_cg_multi", "smvp_tjds_cg_multi",
     "smvp_bicgstab_opts_default", "smvp_csr_bicgstab", "smvp_tjds_bicgstab",
     "smvp_csr_trsv_create", "smvp_trsv_solve", "smvp_trsv_info", "smvp_trsv_schedule", "smvp_trsv_destroy", "smvp_csr_trsv_levels",
     "smvp_csr_pcg_tri", "smvp_tjds_pcg_tri",
@@ -246,6 +246,9 @@ def lib():
         L.smvp_tjds_diagonal.argtypes = [vp, vp, vp]
         L.smvp_csr_pcg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
         L.smvp_tjds_pcg.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
+        ll = C.c_longlong
+        L.smvp_csr_cg_multi.argtypes = [vp, C.POINTER(CgOpts), ci, vp, ll, vp, ll, vp, ll, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
+        L.smvp_tjds_cg_multi.argtypes = [vp, C.POINTER(CgOpts), ci, vp, ll, vp, ll, vp, ll, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
         L.smvp_bicgstab_opts_default.argtypes = [C.POINTER(BicgstabOpts)]
         L.smvp_bicgstab_opts_default.restype = None
         L.smvp_csr_bicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
@@ -696,6 +699,46 @@ def _pcg(fn, handle, b, x, m, x0, max_steps, tol, check_every, stream):
     return r, rr[:r.updates + 1], rz[:r.updates + 1], sigma[:r.steps]
 
 
+def cg_multi_operands(B, X, X0, m, n):
+    """(k, ldb, ldx, ldx0) of the operands of CsrMatrix.cg_multi: B, X and X0 (or None) float64 tensors of shape (n, k) whose rows are
+    contiguous (stride(1) == 1; the leading dimension is stride(0) >= k), m (or None) a contiguous float64 tensor of n elements.
+    Raises ValueError otherwise.  Checks shapes, dtypes and strides only, so it runs on CPU tensors too."""
+    named = [("B", B), ("X", X)] + ([("X0", X0)] if X0 is not None else [])
+    for name, t in named:
+        if not hasattr(t, "stride") or not hasattr(t, "dim") or t.dim() != 2:
+            raise ValueError("%s must be a 2-D tensor" % name)
+        if str(t.dtype) != "torch.float64":
+            raise ValueError("%s must be float64, not %s" % (name, t.dtype))
+        if t.shape[0] != n:
+            raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.shape[0], n))
+    k = B.shape[1]
+    if k < 1 or any(t.shape[1] != k for _, t in named):
+        raise ValueError("B, X and X0 need the same number of columns k >= 1 (they have %s)" % [t.shape[1] for _, t in named])
+    for name, t in named:
+        if t.stride(1) != 1 or t.stride(0) < k:
+            raise ValueError("%s must be row-major with contiguous rows (stride(1) == 1, stride(0) >= k); its strides are %s"
+                             % (name, tuple(t.stride())))
+    if m is not None and (str(m.dtype) != "torch.float64" or m.numel() != n or not m.is_contiguous()):
+        raise ValueError("m must be a contiguous float64 tensor of %d elements (it has %d of %s)" % (n, m.numel(), m.dtype))
+    return k, B.stride(0), X.stride(0), X0.stride(0) if X0 is not None else 0
+
+
+def _cg_multi(fn, handle, n, B, X, m, X0, max_steps, tol, check_every, stream):
+    """smvp_csr_cg_multi / smvp_tjds_cg_multi -> (results, rr_each, rz_each or None, sigma_each): a list of k PcgResult and the
+    histories as (k, max_steps + 1), (k, max_steps + 1) and (k, max_steps) numpy arrays, NaN beyond a column's filled elements
+    (rr, rz: 0 .. updates; sigma: 0 .. steps - 1)."""
+    k, ldb, ldx, ldx0 = cg_multi_operands(B, X, X0, m, n)
+    _device_vectors(B=B, X=X, m=m, X0=X0)
+    o = cg_opts(max_steps, tol, check_every)
+    r = (PcgResult * k)()
+    steps = max(int(max_steps), 0)
+    rr, sigma = np.full((k, steps + 1), np.nan), np.full((k, max(steps, 1)), np.nan)
+    rz = np.full((k, steps + 1), np.nan) if m is not None else None
+    _check(getattr(lib(), fn)(handle, C.byref(o), k, _dev_ptr(B), ldb, _dev_ptr(X0), ldx0, _dev_ptr(X), ldx, _dev_ptr(m), r, _p(rr),
+                              _p(rz) if rz is not None else None, _p(sigma), _stream_ptr(stream)), fn)
+    return list(r), rr, rz, sigma[:, :steps]
+
+
 def bicgstab_opts(max_steps=100, tol=1e-10, check_every=10):
     """smvp_bicgstab_opts_t from smvp_bicgstab_opts_default with the three fields set."""
     o = BicgstabOpts()
@@ -1007,6 +1050,15 @@ class CsrMatrix:
         result.updates + 1 values of r.r and r.z, sigma_each result.steps values of p.Ap.  The stop rule is cg()'s, on r.r."""
         return _pcg("smvp_csr_pcg", self._h, b, x, m, x0, max_steps, tol, check_every, stream)
 
+    def cg_multi(self, B, X, m=None, X0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """k conjugate-gradient runs that share every read of the matrix and every launch (smvp_csr_cg_multi, K20): column v of X
+        receives the solution of A x = B[:, v] from X0[:, v] (None = zeros), by cg()'s rules, or pcg()'s with m given.  B, X and X0
+        are float64 CUDA tensors of shape (rows, k) with contiguous rows -- contiguous, or column slices of wider tensors: the
+        leading dimensions are the tensors' stride(0) --, X may be X0, m has `rows` elements.  Returns (results, rr_each, rz_each or
+        None, sigma_each) after the work on `stream` has finished: a list of k PcgResult, and (k, .) numpy arrays of the histories
+        that hold NaN beyond a column's filled elements.  The product is spmm()'s: the kernel set_kernel chose plays no part."""
+        return _cg_multi("smvp_csr_cg_multi", self._h, self.rows, B, X, m, X0, max_steps, tol, check_every, stream)
+
     def trsv_plan(self, uplo, diag=TRSV_DIAG_STORED, stream=None):
         """A TrsvPlan for the `uplo` triangle of this matrix as stored (smvp_csr_trsv_create, K15): TRSV_LOWER or TRSV_UPPER,
         the diagonal as stored or taken as ones.  Analysed on the host once; close the plan before the matrix."""
@@ -1142,6 +1194,12 @@ class TjdsMatrix:
         ROW_GATHER or TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.pcg.  Afterwards the handle's permuted operand is
         the last direction's: call set_x again before the next spmv."""
         return _pcg("smvp_tjds_pcg", self._h, b, x, m, x0, max_steps, tol, check_every, stream)
+
+    def cg_multi(self, B, X, m=None, X0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
+        """k conjugate-gradient runs that share every read of the matrix and every launch (smvp_tjds_cg_multi, K20): operands and
+        result as CsrMatrix.cg_multi.  The product is spmm()'s, in every mode, ATOMIC and ref-quirks included; the permuted operand
+        of set_x is neither read nor written."""
+        return _cg_multi("smvp_tjds_cg_multi", self._h, self.rows, B, X, m, X0, max_steps, tol, check_every, stream)
 
     def pcg_tri(self, b, x, first, second, m=None, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
         """Conjugate gradients preconditioned with M = T1 diag(m)^-1 T2 on this handle's product in its current mode
