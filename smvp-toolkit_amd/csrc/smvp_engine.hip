@@ -342,7 +342,7 @@ int build_sweep_plan(smvp_csr *h, int want)
 
 // Share of the gathers of a (large) CSR matrix that pull their own 128-byte line of x through the L2, estimated on
 // kSpreadSamples runs of 64 K consecutive entries -- one XCD's turn of the tile kernel -- by linear counting
-// (smvp_kernels.hip: csr_line_spread): distinct lines / entries, 0 ... 1.  -1: too small to sample, or the probe failed.
+// (smvp_kernels.hip: csr_line_spread; the column sweep itself is smvp_colsweep.hip): distinct lines / entries, 0 ... 1.  -1: too small to sample, or the probe failed.
 constexpr int kSpreadSamples = 64;
 double csr_gather_spread(const smvp_csr *h)
 {

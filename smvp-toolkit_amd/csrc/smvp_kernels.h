@@ -1,4 +1,5 @@
-// smvp_kernels.h -- internal interface between the kernel TU and the engine TU.
+// smvp_kernels.h -- internal interface between the kernel TUs and the engine TU.  (The device side of the owner kernel, which
+// only its two launching units see, is smvp_owner_kernel.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,6 +65,11 @@ hipError_t launch_csr_vector(int lanes_per_row, const int *row_ptr, const int *c
 hipError_t launch_csr_stream(int vpt, const int *row_ptr, const int *col_ind, const double *val,
                              const double *x, double *y, const int *tile_row, const int *carry_row,
                              double *carry, int rows, int nnz, int ntiles, hipStream_t stream);
+// Tiles per XCD turn for a launch of `ntiles` tiles: kStreamTileGroup, smaller for small matrices so that
+// the grid (rounded up to a multiple of 8 * group) is not mostly empty blocks.
+// (Groups of 1 ... 2048 were swept in rounds 2 and 5 -- within 2 % from 16 on; profiles/HISTORY_r01_r04.md.)
+// (The arithmetic lives in smvp_tile_map.h, where the host tests it.)
+inline int tile_group(int ntiles, int wanted = kStreamTileGroup) { return tile_group_of(ntiles, wanted); }
 // what an entry of the owner kernel's stream is (see csr_stream_owner)
 constexpr int kFlavorCsr = 0;    // val[j] * x[col_ind[j]]
                                  // (1 was a unit-value CSR: the two-phase TJDS product's second phase until round 5)
@@ -109,9 +115,6 @@ int owner_stamp_slots(int ntiles, int flavor);  // {first, last} tick pairs one 
 constexpr int kRepeatCtlWords = 32 * 66;  // the run's sticky give-up word, 32 shard counters, 32 go words, the top counter (bit 31: abort; the last line), each on a 128-byte line of its own
 constexpr unsigned kRepeatPatienceDefaultUs = 50000;  // how long a workgroup waits at one barrier before the launch gives up
 int owner_repeat_grid(int vpt, int flavor, int ntiles);
-// (the CSR flavours' plain launches live in the second translation unit of smvp_kernels.hip, compiled -DSMVP_TU_ILP with the
-// max-ILP scheduling strategy -- see the Makefile; `extra` is the launcher's OwnerExtra)
-hipError_t launch_owner_csr_ilp(int vpt, int flavor, const OwnerLaunch &l, const void *extra, unsigned grid_x, int group, hipStream_t stream);
 // first_of_run: clears the sticky give-up word too (later launches of the run leave at once when it is set); patience_ticks: of the
 // 100 MHz wall clock (repeat_patience_ticks below)
 hipError_t launch_csr_stream_owner_repeat(int vpt, int flavor, const OwnerLaunch &l, int reps, int grid, unsigned *ctl_words,
@@ -267,5 +270,14 @@ __device__ __forceinline__ double wave_sum_dpp(double v)
     return (r[0] + r[1]) + (r[2] + r[3]);
 }
 
+// The __shfl_down tree over WIDTH lanes (32, 16, ... 1): lane 0 of every group of WIDTH lanes returns the group's sum.
+template <int WIDTH>
+__device__ __forceinline__ double shfl_down_sum(double v)
+{
+#pragma unroll
+    for (int off = WIDTH / 2; off > 0; off >>= 1)
+        v += __shfl_down(v, off, WIDTH);
+    return v;
+}
 
 }  // namespace smvp

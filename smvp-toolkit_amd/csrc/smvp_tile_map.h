@@ -22,7 +22,7 @@ inline int tile_group_of(int ntiles, int wanted)
 inline unsigned tile_grid_of(int ntiles, int group) { return (unsigned)((ntiles + 8 * group - 1) / (8 * group)) * 8u * group; }
 
 // Blocks are dealt round-robin over the 8 XCDs; XCD i takes `group` consecutive tiles out of every run of 8 * group
-// (the measurements are beside K2 in smvp_kernels.hip).  A permutation of every round of 8 * group blocks, hence of
+// (the measurements are beside K2' in smvp_owner_kernel.h).  A permutation of every round of 8 * group blocks, hence of
 // [0, grid) for a grid of whole rounds.
 SMVP_HOST_DEVICE inline __attribute__((always_inline)) int tile_of_block(int block, int group)
 {

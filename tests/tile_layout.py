@@ -18,7 +18,7 @@ KINDS = ("tail", "tail_wide_one", "tail_wide_all", "giant", "exact", "exact_less
 
 # --------------------------------------------------------------------------------------------------- the kernel's formula
 def lane_entry(vpt, t, k):
-    """Offset in the tile of entry k (0 ... vpt - 1) of thread t: owner_body's lane_entry (csrc/smvp_kernels.hip).  The product
+    """Offset in the tile of entry k (0 ... vpt - 1) of thread t: owner_body's lane_entry (csrc/smvp_owner_kernel.h).  The product
     goes to prod[] at the same offset."""
     wave, lane = t // WAVE, t % WAVE
     if vpt == 1:

@@ -18,11 +18,11 @@ import smvp_toolkit_amd as sm
 
 # ---------------------------------------------------------------------------------------------------------- launch arithmetic
 # Mirrors of csrc/smvp_tile_map.h (tile_group_of, tile_grid_of), smvp_kernels.h (kStreamTileGroup, kTjdsTileGroup) and the shard
-# rule of launch_csr_stream_owner_repeat (smvp_kernels.hip).
+# rule of launch_csr_stream_owner_repeat (smvp_owner.hip).
 WANTED_GROUP = {"csr": 64, "tjds": 32}
 TILES = (256, 1024, 2048)
 REPEAT_RING, GRAPH_RING = 1024, 256        # products per repeating launch / per graph replay (smvp_run.hip)
-# (vpt, flavor) of the instantiations of csr_stream_owner_repeat (SMVP_REPEAT_FORMS); flavours as in smvp_kernels.h
+# (vpt, flavor) of the instantiations of csr_stream_owner_repeat (SMVP_OWNER_REPEAT_FORMS, smvp_owner_kernel.h); flavours as in smvp_kernels.h
 CSR, TJDS_K, TJDS_S, TJDS_H, CSR16 = 0, 2, 3, 4, 5
 REPEAT_FORMS = frozenset([(1, CSR), (4, CSR), (8, CSR), (4, CSR16), (8, CSR16), (1, TJDS_S), (4, TJDS_S), (8, TJDS_S),
                           (1, TJDS_H), (4, TJDS_H), (8, TJDS_H)])

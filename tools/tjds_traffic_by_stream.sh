@@ -31,9 +31,10 @@ PY
 }
 for mask in 0 1 2 4 8 3 7 15; do
   mkdir -p /tmp/smvp_diag/b$mask
-  /opt/rocm/bin/hipcc $FLAGS -DSMVP_TJDS_NEUTRALISE=$mask -c $PKG/csrc/smvp_kernels.hip -o /tmp/smvp_diag/b$mask/smvp_kernels.o || exit 1
-  OBJ=$(ls $PKG/build/*.o | grep -v smvp_kernels.o)
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/smvp_diag/b$mask/libsmvp_amd.so $OBJ /tmp/smvp_diag/b$mask/smvp_kernels.o -lpthread -ldl || exit 1
+  # (the TJDS flavours of the tile kernel are instantiated in smvp_owner.hip, default scheduling strategy; every other object is the build's)
+  /opt/rocm/bin/hipcc $FLAGS -DSMVP_TJDS_NEUTRALISE=$mask -c $PKG/csrc/smvp_owner.hip -o /tmp/smvp_diag/b$mask/smvp_owner.o || exit 1
+  OBJ=$(ls $PKG/build/*.o | grep -v '/smvp_owner\.o$')
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/smvp_diag/b$mask/libsmvp_amd.so $OBJ /tmp/smvp_diag/b$mask/smvp_owner.o -lpthread -ldl || exit 1
   pass /tmp/smvp_diag/b$mask/libsmvp_amd.so "neutralised mask $mask (1 x_perm, 2 val in place, 4 val cache, 8 overflow)" gather:half:0:2
 done 2>&1 | tee "$OUT/by_stream.txt"
 for cache in 0 1 2 4; do
