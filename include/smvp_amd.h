@@ -827,7 +827,8 @@ int smvp_tjds_cg_multi(smvp_tjds_t *h, const smvp_cg_opts_t *opts, int k, const 
  * incomplete factorisation that gives it two triangles on one handle is smvp_csr_ilu0_create, K17, below that. */
 enum { SMVP_TRSV_LOWER = 0, SMVP_TRSV_UPPER = 1 };
 enum { SMVP_TRSV_DIAG_STORED = 0, SMVP_TRSV_DIAG_UNIT = 1 };
-typedef struct smvp_trsv smvp_trsv_t; /* a plan: borrows the handle's arrays, owns level_ptr / order on the device */
+typedef struct smvp_trsv smvp_trsv_t; /* a plan: borrows the handle's arrays, owns level_ptr / order on the device (a sweeps plan,
+                                         K21 below: the rows' storage ranges and two scratch vectors) */
 typedef struct smvp_trsv_info {
     unsigned struct_size;  /* set by the caller to sizeof(smvp_trsv_info_t) before the call; another size is SMVP_ERR_INVALID */
     int levels;
@@ -867,6 +868,56 @@ int smvp_trsv_info(const smvp_trsv_t *t, smvp_trsv_info_t *out);
 int smvp_trsv_schedule(const smvp_trsv_t *t, int *level_ptr, int *order);
 void smvp_trsv_destroy(smvp_trsv_t *t);
 int smvp_csr_trsv_levels(int rows, const int *row_ptr, const int *col_ind, int uplo, int *level_of_row, int *levels);
+
+/* ------------------------------------------------- Jacobi sweeps on a triangular system, as a plan */
+/* A fixed number of Jacobi sweeps on T x = b instead of the exact solve, kernel K21 (new: the reference only multiplies).  A
+ * preconditioner is an approximation anyway (Anzt, Chow, Dongarra: iterative sparse triangular solves for preconditioning), and a
+ * sweep is one fully parallel pass over the triangle: a solve is sweeps + 1 launches whatever the number of levels.  The result of
+ * smvp_csr_trsv_create_sweeps is an ordinary smvp_trsv_t: smvp_trsv_solve, _info, _schedule, _destroy and every solver that takes
+ * plans (K16, K18, K19) accept it as they stand.
+ *
+ * The per-row rule is K15's: d_i is the sum from +0.0 of the stored (i, i) in ascending storage position (not read for DIAG_UNIT);
+ * s_i(x) the sum from +0.0 of val[p] * x[c] over the stored entries inside the triangle in ascending storage position, the product
+ * rounded, then the sum, no FMA; the other triangle is skipped.  The solve is
+ *   x(0)_i   = (b_i - (+0.0)) / d_i            (DIAG_UNIT: b_i - (+0.0), which is b_i, a signed zero included)
+ *   x(m+1)_i = (b_i - s_i(x(m))) / d_i         (DIAG_UNIT: b_i - s_i(x(m))),   m = 0 .. sweeps - 1
+ *   x = x(sweeps)
+ * Every sweep reads only the previous iterate, never an element written by the same launch: every element of every iterate has
+ * one right answer, whatever the order between workgroups.  Consequences:
+ *   - sweeps = 0 is a division by the diagonal.
+ *   - x(m)_i equals the exact solve's x_i, bit for bit, for every row of level <= m (a row of level l reads rows of levels < l
+ *     only, by the same rule in the same order).  So sweeps >= levels - 1 gives smvp_trsv_solve's result on a plan of
+ *     smvp_csr_trsv_create, bit for bit; smvp_trsv_info's `levels` says which count is exact.
+ *   - For a symmetric A the LOWER and UPPER plans with the same `sweeps` and m = diagonal() give a symmetric positive definite
+ *     M^-1 = P^T D P (P = sum of the first sweeps + 1 powers of -D^-1 L, applied to D^-1), and so do the LOWER / UNIT and
+ *     UPPER / STORED plans of its ILU(0): smvp_*_pcg_tri stays valid.  Unequal sweep counts are the caller's risk, as M's
+ *     symmetry always was.
+ *   - A missing or zero diagonal gives +-Inf or NaN by the same rules, unvalidated.
+ *   - Where a row's off-diagonals inside the triangle outweigh its diagonal, intermediate iterates grow before nilpotency brings
+ *     them back.  Nothing about that is validated.
+ *
+ *   - smvp_csr_trsv_create_sweeps makes smvp_csr_trsv_create's checks and refusals (plain CSR, square, no row block, no capturing
+ *     stream) and runs the same host analysis: levels, missing_diagonals, max_level_width and smvp_trsv_schedule mean what they
+ *     mean for an exact plan.  From col_ind it computes one storage range [begin_i, end_i) per row, the smallest that holds all of
+ *     the row's entries inside the triangle and (DIAG_STORED) on the diagonal; a sweep walks only that range, which adds the same
+ *     values in the same order as a walk of the row, everything outside being of the skipped kind.  Rows with ascending columns
+ *     get a tight range (a sweep then reads half of a full matrix's col_ind); unsorted rows a loose one that is still right.
+ *     The plan owns begin and end (n ints each) and two scratch vectors of n doubles between which a solve's iterates alternate;
+ *     it borrows row_ptr / col_ind / val as K15's plans do: `val` changed in place is seen by the next solve, a changed
+ *     structure needs a new plan.  0 <= sweeps <= SMVP_TRSV_MAX_SWEEPS, anything else is SMVP_ERR_INVALID.
+ *   - smvp_trsv_solve on such a plan: launch 0 writes x(0) reading only b; launch m reads b and the scratch vector launch m - 1
+ *     wrote; the last launch writes d_x, which is never read, so d_x == d_b works as before.  Nothing depends on what the scratch
+ *     vectors held.  It allocates nothing, synchronises nothing, and is capturable from the plan's first call: a plain chain of
+ *     kernels.  A plan is used by one stream at a time (two solves in flight would share the scratch vectors).
+ *   - smvp_trsv_info on such a plan: launches = sweeps + 1 (0 for n = 0); chains = 0 and chain_width = 0; lanes_per_row as used
+ *     (K15's rule on the ranges' mean and longest length); entries = the stored entries inside the ranges, which one sweep reads
+ *     (launch 0 reads val on the diagonal only, and nothing at all for DIAG_UNIT); plan_bytes = the bytes of the four buffers.
+ *   - smvp_trsv_sweeps: *sweeps = the plan's count, -1 for a plan of smvp_csr_trsv_create.  A NULL t or sweeps is SMVP_ERR_INVALID.
+ * Out of scope: TJDS and sharded handles, k right-hand sides, a sweep count chosen by the library, a residual-based stop inside a
+ * solve, a compacted copy of the triangle, asynchronous sweeps that read the iterate they write, block-Jacobi variants. */
+enum { SMVP_TRSV_MAX_SWEEPS = 4096 };
+int smvp_csr_trsv_create_sweeps(smvp_trsv_t **out, const smvp_csr_t *h, int uplo, int diag, int sweeps, void *stream);
+int smvp_trsv_sweeps(const smvp_trsv_t *t, int *sweeps);   /* -1 for a plan of smvp_csr_trsv_create */
 
 /* ------------------------------------------------- conjugate gradients preconditioned by two triangular solves */
 /* Conjugate gradients on a square n x n handle's own product, preconditioned with M = T1 diag(m)^-1 T2, kernel K16 (new: the

@@ -13,6 +13,7 @@
 // Exit status 0 unless a call that must succeed fails (an input the library REJECTS is a pass: what is looked for is what the
 // sanitizer reports, which ends the process by itself).
 #include "smvp_amd.h"
+#include "smvp_common.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -237,6 +238,23 @@ static int run_synth(const std::string &tmp)
         MUST(smvp_csr_trsv_levels(4, mix_rp.data(), mix_c.data(), uplo, lv.data(), &levels));
     if (levels != 2 || lv[0] != 1 || lv[3] != 0)
         ++g_bad, fprintf(stderr, "FAILED: the mixed case's upper triangle: %d levels, row 0 at %d\n", levels, lv[0]);
+    // K21's storage ranges on the same arrays: row 0 (columns 3 0) has nothing in its lower triangle under a unit diagonal and
+    // its diagonal at position 1 with the stored one, row 2 (columns 2 1 1 0) its diagonal first, the empty row an empty range
+    for (int uplo : {SMVP_TRSV_LOWER, SMVP_TRSV_UPPER})
+        for (int diag : {SMVP_TRSV_DIAG_STORED, SMVP_TRSV_DIAG_UNIT}) {
+            std::vector<int> begin, end;
+            long long inside = 0;
+            int longest = 0;
+            smvp::trsv_ranges(4, mix_rp.data(), mix_c.data(), uplo, diag, &begin, &end, &inside, &longest);
+            const bool lower = uplo == SMVP_TRSV_LOWER, stored = diag == SMVP_TRSV_DIAG_STORED;
+            if (begin[3] != 9 || end[3] != 9 || (lower && (begin[0] != (stored ? 1 : 0) || end[0] != (stored ? 2 : 0) || begin[2] != (stored ? 5 : 6) || end[2] != 9)))
+                ++g_bad, fprintf(stderr, "FAILED: the mixed case's ranges, uplo %d, diag %d\n", uplo, diag);
+            long long sum = 0;
+            for (int i = 0; i < 4; ++i)
+                sum += end[(size_t)i] - begin[(size_t)i];
+            if (sum != inside || longest > 4)
+                ++g_bad, fprintf(stderr, "FAILED: the mixed case's range total, uplo %d, diag %d\n", uplo, diag);
+        }
     mix_c[4] = 4;  // a column past the last row, a decreasing row_ptr, a bad uplo, null arrays: refused before anything is read or written
     rc = smvp_csr_trsv_levels(4, mix_rp.data(), mix_c.data(), SMVP_TRSV_UPPER, lv.data(), &levels);
     mix_c[4] = 0, mix_rp[2] = 1;

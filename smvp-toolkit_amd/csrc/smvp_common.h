@@ -30,6 +30,9 @@ struct TrsvLaunch {
 };
 int trsv_analyse(int rows, const int *row_ptr, const int *col_ind, int uplo, TrsvSchedule *out);
 void trsv_launches(const std::vector<int> &level_ptr, int chain_width, std::vector<TrsvLaunch> *out, int *chains);
+// K21, a sweeps plan's storage range per row: what a sweep reads of the row; their total and the longest
+void trsv_ranges(int rows, const int *row_ptr, const int *col_ind, int uplo, int diag, std::vector<int> *begin, std::vector<int> *end,
+                 long long *entries, int *longest);
 
 // K17, what an ILU(0) asks of a CSR pattern (smvp_ilu0_plan.cpp): smvp_csr_ilu0_check under the caller's name `fn`, the arguments
 // checked for null already

@@ -27,6 +27,10 @@
 //                       its rows' lengths (or without a row).  What the next level needs that does not depend on x -- its rows,
 //                       their bounds, b_i -- is loaded in front of the barrier.
 // A wide level of more than 2^31 / T rows is cut into launches of that many (launch_level: fewer than 2^32 threads each).
+//   trsv_sweep_rows<T, FIRST>  K21 (smvp_csr_trsv_create_sweeps): not the solve but a fixed number of Jacobi sweeps on it, every
+//                       sweep one launch of trsv_level_rows's shape over ALL rows -- natural order, a storage range per row instead
+//                       of the whole row, the operand iterate in a scratch vector of the plan's (two, alternating), so that no
+//                       launch reads what it writes.  A row of level l has the exact solve's bits after l sweeps.
 //
 // x is read and written in the same launch (other rows'; in a chain, rows of earlier levels) and d_x may be d_b: neither pointer is
 // __restrict__ or const __restrict__, or the compiler could serve them from the scalar or read-only path and read stale values.
@@ -71,7 +75,8 @@ __device__ inline double trsv_from_lane_below(double v)
 // base + j * kTrsvChunk on (those at z and beyond are nobody's).  trsv_load turns them into the operands of the two sums: ws = val *
 // x[c] inside the triangle, wd = val on the diagonal, +0.0 for everything else.  Adding +0.0 is exact for every value a sum from
 // +0.0 can take (it is never -0.0: only -0.0 + -0.0 gives that), so a skipped entry may be added as +0.0 and the loop below needs
-// no masks.
+// no masks.  GATHER = false (K21's launch 0) loads no x and no val inside the triangle: only wd is meant to be used.
+template <bool GATHER = true>
 __device__ inline void trsv_load(const int *__restrict__ col_ind, const double *__restrict__ val, const double *x, long long p0, int z,
                                  int row, int upper, int unit, double (&ws)[kTrsvChunk], double (&wd)[kTrsvChunk])
 {
@@ -83,8 +88,8 @@ __device__ inline void trsv_load(const int *__restrict__ col_ind, const double *
 #pragma unroll
     for (int u = 0; u < kTrsvChunk; ++u) {
         kind[u] = trsv_kind(c[u], row, upper, unit);
-        v[u] = kind[u] ? val[p0 + u] : 0.0;
-        xv[u] = kind[u] == 1 ? x[c[u]] : 0.0;  // an earlier level's element: an earlier launch's, or stored in front of a barrier
+        v[u] = (GATHER ? kind[u] != 0 : kind[u] == 2) ? val[p0 + u] : 0.0;
+        xv[u] = GATHER && kind[u] == 1 ? x[c[u]] : 0.0;  // an earlier level's element: an earlier launch's, or stored in front of a barrier
     }
 #pragma unroll
     for (int u = 0; u < kTrsvChunk; ++u) {
@@ -125,6 +130,7 @@ __device__ inline int trsv_last_lane(int a, int z, int T) { return z > a ? ((z -
 // A group's row from its second pass on (`base`: where that begins); s and d hold the first pass's sums in lane T - 1 (a further
 // pass follows a full one) and are handed to every lane of the group before each further pass.  kTrsvTrips passes' loads are in
 // flight together.
+template <bool GATHER = true>
 __device__ inline void trsv_further_passes(const int *__restrict__ col_ind, const double *__restrict__ val, const double *x, long long base,
                                            int z, int row, int T, int lane, int shift, int upper, int unit, double &s, double &d)
 {
@@ -132,7 +138,7 @@ __device__ inline void trsv_further_passes(const int *__restrict__ col_ind, cons
         double ws[kTrsvTrips][kTrsvChunk], wd[kTrsvTrips][kTrsvChunk];
 #pragma unroll
         for (int u = 0; u < kTrsvTrips; ++u)
-            trsv_load(col_ind, val, x, base + ((long long)u * T + lane) * kTrsvChunk, z, row, upper, unit, ws[u], wd[u]);
+            trsv_load<GATHER>(col_ind, val, x, base + ((long long)u * T + lane) * kTrsvChunk, z, row, upper, unit, ws[u], wd[u]);
 #pragma unroll
         for (int u = 0; u < kTrsvTrips; ++u) {
             const int n = trsv_pass_lanes(base + (long long)u * T * kTrsvChunk, z, T);
@@ -184,6 +190,56 @@ __global__ __launch_bounds__(kVectorBlock) void trsv_level_rows(const int *__res
         trsv_further_passes(col_ind, val, x, (long long)a[i] + T * kTrsvChunk, z[i], row[i], T, lane, shift, upper, unit, s, d);
         if (lane == trsv_last_lane(a[i], z[i], T) && row[i] >= 0)
             x[row[i]] = unit ? bi[i] - s : (bi[i] - s) / d;
+    }
+}
+
+// K21, one Jacobi sweep on the triangular system: xout_i = (b_i - s_i(xin)) / d_i for rows lo .. hi - 1 in natural order, the shape
+// of trsv_level_rows with three differences.  There is no `order`: neighbouring groups take neighbouring rows and write neighbouring
+// elements.  A row's bounds are the plan's storage range [begin_i, end_i), not the whole row: half of col_ind for a matrix stored in
+// full with ascending columns.  And the operand iterate xin is another buffer than xout (the plan's scratch vectors, never d_x or
+// d_b), written by the launch before and by nobody in this one, so it is const __restrict__; b and xout are not, d_x may be d_b.
+// FIRST is launch 0, x(0)_i = (b_i - (+0.0)) / d_i: no gather and no val inside the triangle is loaded (xin is null), and with a
+// unit diagonal not even the bounds.  b - (+0.0) is b for every b, a signed zero included.
+template <int T, bool FIRST>
+__global__ __launch_bounds__(kVectorBlock) void trsv_sweep_rows(const int *__restrict__ col_ind, const double *__restrict__ val,
+                                                                 const int *__restrict__ begin, const int *__restrict__ end, const double *b,
+                                                                 const double *__restrict__ xin, double *xout, long long lo, long long hi,
+                                                                 int upper, int unit)
+{
+    constexpr int G = 64 / T;  // groups of a wavefront
+    const long long wave = ((long long)blockIdx.x * kVectorBlock + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & (T - 1);
+    const int shift = threadIdx.x & 63 & ~(T - 1);  // where the group's lanes lie in the wavefront
+    const long long k0 = lo + wave * (kTrsvRows * G) + (shift / T);
+    int row[kTrsvRows], a[kTrsvRows], z[kTrsvRows];
+    double bi[kTrsvRows], ws[kTrsvRows][kTrsvChunk], wd[kTrsvRows][kTrsvChunk];
+#pragma unroll
+    for (int i = 0; i < kTrsvRows; ++i) {
+        const long long k = k0 + i * G;
+        row[i] = k < hi ? (int)k : -1;
+        a[i] = z[i] = 0;
+        bi[i] = 0.0;
+        if (row[i] >= 0) {
+            if (!(FIRST && unit)) {
+                a[i] = begin[row[i]];
+                z[i] = end[row[i]];
+            }
+            if (lane == trsv_last_lane(a[i], z[i], T))
+                bi[i] = b[row[i]];  // read by the lane that writes xout[row]: on the last launch d_b may be d_x
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kTrsvRows; ++i)  // the first pass of every row of the wavefront: all their loads before any addition
+        trsv_load<!FIRST>(col_ind, val, xin, (long long)a[i] + lane * kTrsvChunk, z[i], row[i], upper, unit, ws[i], wd[i]);
+#pragma unroll
+    for (int i = 0; i < kTrsvRows; ++i) {
+        double s = 0.0, d = 0.0;
+        trsv_scan(ws[i], wd[i], trsv_pass_lanes(a[i], z[i], T), lane, s, d);
+        trsv_further_passes<!FIRST>(col_ind, val, xin, (long long)a[i] + T * kTrsvChunk, z[i], row[i], T, lane, shift, upper, unit, s, d);
+        if (FIRST)
+            s = 0.0;
+        if (lane == trsv_last_lane(a[i], z[i], T) && row[i] >= 0)
+            xout[row[i]] = unit ? bi[i] - s : (bi[i] - s) / d;
     }
 }
 
@@ -294,6 +350,26 @@ void launch_level(const CsrView &m, const int *order, const double *b, double *x
     }
 }
 
+// one sweep over rows 0 .. n - 1, cut like a wide level (xin == nullptr: launch 0)
+template <int T>
+void launch_sweep(const CsrView &m, const int *begin, const int *end, const double *b, const double *xin, double *xout, int unit,
+                  int upper, hipStream_t stream)
+{
+    const long long chunk = ((long long)1 << 31) / T;
+    constexpr long long kWaveRows = (long long)kTrsvRows * (64 / T);
+    for (long long k0 = 0; k0 < m.rows; k0 += chunk) {
+        const long long n = m.rows - k0 < chunk ? m.rows - k0 : chunk;
+        const long long waves = (n + kWaveRows - 1) / kWaveRows;
+        const unsigned grid = (unsigned)((waves * 64 + kVectorBlock - 1) / kVectorBlock);
+        if (xin)
+            hipLaunchKernelGGL((trsv_sweep_rows<T, false>), dim3(grid), dim3(kVectorBlock), 0, stream, m.d_col_ind, m.d_val, begin, end, b,
+                               xin, xout, k0, k0 + n, upper, unit);
+        else
+            hipLaunchKernelGGL((trsv_sweep_rows<T, true>), dim3(grid), dim3(kVectorBlock), 0, stream, m.d_col_ind, m.d_val, begin, end, b,
+                               xin, xout, k0, k0 + n, upper, unit);
+    }
+}
+
 int pow2_lanes(double mean)
 {
     int p = 2;
@@ -314,6 +390,11 @@ struct smvp_trsv {
     std::vector<smvp::TrsvLaunch> launches;
     long long entries = 0;
     double plan_bytes = 0.0, build_ms = 0.0;
+    // K21, a sweeps plan (sweeps >= 0; -1: an exact plan, which has none of these): every row's storage range and the two vectors
+    // a solve's iterates alternate between.  It has no d_level_ptr / d_order and no launches: the schedule is kept for the caller.
+    int sweeps = -1;
+    int *d_begin = nullptr, *d_end = nullptr;
+    double *d_scratch[2] = {nullptr, nullptr};
 };
 
 extern "C" void smvp_trsv_destroy(smvp_trsv_t *t)
@@ -321,32 +402,42 @@ extern "C" void smvp_trsv_destroy(smvp_trsv_t *t)
     if (!t)
         return;
     smvp::DeviceScope on(t->m.device);
-    for (void *q : {(void *)t->d_level_ptr, (void *)t->d_order})
+    for (void *q : {(void *)t->d_level_ptr, (void *)t->d_order, (void *)t->d_begin, (void *)t->d_end, (void *)t->d_scratch[0],
+                    (void *)t->d_scratch[1]})
         if (q)
             (void)hipFree(q);
     delete t;
 }
 
-extern "C" int smvp_csr_trsv_create(smvp_trsv_t **out, const smvp_csr_t *h, int uplo, int diag, void *stream)
+namespace smvp {
+
+namespace {
+
+// smvp_csr_trsv_create (sweeps = -1) and smvp_csr_trsv_create_sweeps under the caller's name `fn`: the same checks, the same copy
+// back of col_ind and the same host analysis; then the exact plan's schedule on the device, or K21's ranges and scratch vectors.
+int trsv_create(const char *fn, smvp_trsv_t **out, const smvp_csr_t *h, int uplo, int diag, int sweeps, void *stream)
 {
-    using namespace smvp;
-    if (!out || !h)
-        return fail(SMVP_ERR_INVALID, "smvp_csr_trsv_create: null %s", !out ? "out" : "handle");
+    if (!out)
+        return fail(SMVP_ERR_INVALID, "%s: null out", fn);
     if (uplo != SMVP_TRSV_LOWER && uplo != SMVP_TRSV_UPPER)
-        return fail(SMVP_ERR_INVALID, "smvp_csr_trsv_create: uplo = %d is neither SMVP_TRSV_LOWER nor SMVP_TRSV_UPPER", uplo);
+        return fail(SMVP_ERR_INVALID, "%s: uplo = %d is neither SMVP_TRSV_LOWER nor SMVP_TRSV_UPPER", fn, uplo);
     if (diag != SMVP_TRSV_DIAG_STORED && diag != SMVP_TRSV_DIAG_UNIT)
-        return fail(SMVP_ERR_INVALID, "smvp_csr_trsv_create: diag = %d is neither SMVP_TRSV_DIAG_STORED nor SMVP_TRSV_DIAG_UNIT", diag);
+        return fail(SMVP_ERR_INVALID, "%s: diag = %d is neither SMVP_TRSV_DIAG_STORED nor SMVP_TRSV_DIAG_UNIT", fn, diag);
+    if (sweeps < -1 || sweeps > SMVP_TRSV_MAX_SWEEPS)
+        return fail(SMVP_ERR_INVALID, "%s: sweeps = %d is outside [0, %d]", fn, sweeps, SMVP_TRSV_MAX_SWEEPS);
+    if (!h)
+        return fail(SMVP_ERR_INVALID, "%s: null handle", fn);
     const CsrView m = csr_view(h);
     if (m.flavor != kFlavorCsr)
-        return fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_trsv_create: plain CSR handles only (this one belongs to a TJDS matrix)");
+        return fail(SMVP_ERR_UNSUPPORTED, "%s: plain CSR handles only (this one belongs to a TJDS matrix)", fn);
     if (m.first_row != 0)
-        return fail(SMVP_ERR_UNSUPPORTED, "smvp_csr_trsv_create: a row block (first_row = %lld) holds no triangle of its own", m.first_row);
+        return fail(SMVP_ERR_UNSUPPORTED, "%s: a row block (first_row = %lld) holds no triangle of its own", fn, m.first_row);
     if (m.rows != m.cols)
-        return fail(SMVP_ERR_INVALID, "smvp_csr_trsv_create: the handle's matrix is %d x %d, not square", m.rows, m.cols);
+        return fail(SMVP_ERR_INVALID, "%s: the handle's matrix is %d x %d, not square", fn, m.rows, m.cols);
     DeviceScope on(m.device);
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = refuse_capture(st, "smvp_csr_trsv_create: the stream is capturing (the call copies back, allocates and waits: create the "
-                                    "plan outside the capture)"))
+    const std::string why = std::string(fn) + ": the stream is capturing (the call copies back, allocates and waits: create the plan outside the capture)";
+    if (int rc = refuse_capture(st, why.c_str()))
         return rc;
     const double t0 = wall_ms();
     std::vector<int> col((size_t)m.nnz);
@@ -355,28 +446,76 @@ extern "C" int smvp_csr_trsv_create(smvp_trsv_t **out, const smvp_csr_t *h, int 
     HIP_TRY(hipStreamSynchronize(st));
     const int asked = option("trsv_chain_width", kTrsvChainWidth);
     smvp_trsv *t = new smvp_trsv;
-    t->m = m, t->uplo = uplo, t->diag = diag;
-    t->chain_width = asked >= 4 * kVectorBlock ? 4 * kVectorBlock : asked >= 2 * kVectorBlock ? 2 * kVectorBlock : kVectorBlock;
+    t->m = m, t->uplo = uplo, t->diag = diag, t->sweeps = sweeps;
     int rc = trsv_analyse(m.rows, m.h_row_ptr, col.data(), uplo, &t->sched);
-    if (rc == SMVP_OK)
-        rc = upload(&t->d_level_ptr, t->sched.level_ptr);
-    if (rc == SMVP_OK)
-        rc = upload(&t->d_order, t->sched.order);
+    const bool by_mean = option("trsv_lanes_by_mean", 0) != 0;
+    if (sweeps < 0) {
+        t->chain_width = asked >= 4 * kVectorBlock ? 4 * kVectorBlock : asked >= 2 * kVectorBlock ? 2 * kVectorBlock : kVectorBlock;
+        if (rc == SMVP_OK)
+            rc = upload(&t->d_level_ptr, t->sched.level_ptr);
+        if (rc == SMVP_OK)
+            rc = upload(&t->d_order, t->sched.order);
+        if (rc == SMVP_OK) {
+            trsv_launches(t->sched.level_ptr, t->chain_width, &t->launches, &t->chains);
+            t->entries = t->sched.off_entries + (diag == SMVP_TRSV_DIAG_STORED ? t->sched.diag_entries : 0);
+            // lanes a row of a wide level gets: from the geometric mean of the triangle's mean and longest row, over the chunk a lane
+            // takes.  The mean alone (csr_vector_rows's rule) gave memplus, mean 4 and rows of up to 574, two lanes, and a level's
+            // launch then lasts as long as its longest row's 72 passes; option trsv_lanes_by_mean = 1 keeps the mean's rule for the
+            // comparison
+            const double mean = m.rows > 0 ? (double)(t->sched.off_entries + t->sched.diag_entries) / m.rows : 0.0;
+            t->lanes = pow2_lanes((by_mean ? mean : std::sqrt(mean * t->sched.max_row_entries)) / kTrsvChunk);
+            t->plan_bytes = 4.0 * (double)(std::max<size_t>(t->sched.level_ptr.size(), 4) + std::max<size_t>(t->sched.order.size(), 4));
+        }
+    } else if (rc == SMVP_OK) {
+        std::vector<int> begin, end;
+        int longest = 0;
+        trsv_ranges(m.rows, m.h_row_ptr, col.data(), uplo, diag, &begin, &end, &t->entries, &longest);
+        rc = upload(&t->d_begin, begin);
+        if (rc == SMVP_OK)
+            rc = upload(&t->d_end, end);
+        const size_t held = std::max<size_t>((size_t)m.rows, 4);
+        auto scratch = [&](int k) {
+            HIP_TRY(hipMalloc((void **)&t->d_scratch[k], held * sizeof(double)));
+            return (int)SMVP_OK;
+        };
+        for (int k = 0; k < 2 && rc == SMVP_OK; ++k)
+            rc = scratch(k);
+        // lanes per row by K15's rule, from the ranges' mean and longest length
+        const double mean = m.rows > 0 ? (double)t->entries / m.rows : 0.0;
+        t->lanes = pow2_lanes((by_mean ? mean : std::sqrt(mean * longest)) / kTrsvChunk);
+        t->plan_bytes = (double)held * (2.0 * sizeof(int) + 2.0 * sizeof(double));
+    }
     if (rc != SMVP_OK) {
         smvp_trsv_destroy(t);
         return rc;
     }
     std::vector<int>().swap(t->sched.level_of_row);  // (the schedule is what a solve and smvp_trsv_schedule need)
-    trsv_launches(t->sched.level_ptr, t->chain_width, &t->launches, &t->chains);
-    t->entries = t->sched.off_entries + (diag == SMVP_TRSV_DIAG_STORED ? t->sched.diag_entries : 0);
-    // lanes a row of a wide level gets: from the geometric mean of the triangle's mean and longest row, over the chunk a lane takes.
-    // The mean alone (csr_vector_rows's rule) gave memplus, mean 4 and rows of up to 574, two lanes, and a level's launch then lasts
-    // as long as its longest row's 72 passes; option trsv_lanes_by_mean = 1 keeps the mean's rule for the comparison
-    const double mean = m.rows > 0 ? (double)(t->sched.off_entries + t->sched.diag_entries) / m.rows : 0.0;
-    t->lanes = pow2_lanes((option("trsv_lanes_by_mean", 0) ? mean : std::sqrt(mean * t->sched.max_row_entries)) / kTrsvChunk);
-    t->plan_bytes = 4.0 * (double)(std::max<size_t>(t->sched.level_ptr.size(), 4) + std::max<size_t>(t->sched.order.size(), 4));
     t->build_ms = wall_ms() - t0;
     *out = t;
+    return SMVP_OK;
+}
+
+}  // namespace
+
+}  // namespace smvp
+
+extern "C" int smvp_csr_trsv_create(smvp_trsv_t **out, const smvp_csr_t *h, int uplo, int diag, void *stream)
+{
+    return smvp::trsv_create("smvp_csr_trsv_create", out, h, uplo, diag, -1, stream);
+}
+
+extern "C" int smvp_csr_trsv_create_sweeps(smvp_trsv_t **out, const smvp_csr_t *h, int uplo, int diag, int sweeps, void *stream)
+{
+    if (sweeps < 0)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_csr_trsv_create_sweeps: sweeps = %d is outside [0, %d]", sweeps, SMVP_TRSV_MAX_SWEEPS);
+    return smvp::trsv_create("smvp_csr_trsv_create_sweeps", out, h, uplo, diag, sweeps, stream);
+}
+
+extern "C" int smvp_trsv_sweeps(const smvp_trsv_t *t, int *sweeps)
+{
+    if (!t || !sweeps)
+        return smvp::fail(SMVP_ERR_INVALID, "smvp_trsv_sweeps: null %s", !t ? "plan" : "sweeps");
+    *sweeps = t->sweeps;
     return SMVP_OK;
 }
 
@@ -402,6 +541,21 @@ int smvp::trsv_device(const smvp_trsv_t *t) { return t->m.device; }
 int smvp::trsv_enqueue(const char *fn, smvp_trsv_t *t, const double *d_b, double *d_x, hipStream_t st)
 {
     const int upper = t->uplo == SMVP_TRSV_UPPER, unit = t->diag == SMVP_TRSV_DIAG_UNIT;
+    // K21: launch 0 writes x(0) from b alone; launch m reads b and scratch[(m - 1) & 1]; every launch but the last writes
+    // scratch[m & 1], the last d_x.  d_x is never read, and every element of a scratch vector is written by the launch before the
+    // one that reads it.
+    for (int m = 0; t->sweeps >= 0 && t->m.rows > 0 && m <= t->sweeps; ++m) {
+        const double *in = m ? t->d_scratch[(m - 1) & 1] : nullptr;
+        double *out = m == t->sweeps ? d_x : t->d_scratch[m & 1];
+        switch (t->lanes) {
+        case 2: launch_sweep<2>(t->m, t->d_begin, t->d_end, d_b, in, out, unit, upper, st); break;
+        case 4: launch_sweep<4>(t->m, t->d_begin, t->d_end, d_b, in, out, unit, upper, st); break;
+        case 8: launch_sweep<8>(t->m, t->d_begin, t->d_end, d_b, in, out, unit, upper, st); break;
+        case 16: launch_sweep<16>(t->m, t->d_begin, t->d_end, d_b, in, out, unit, upper, st); break;
+        case 32: launch_sweep<32>(t->m, t->d_begin, t->d_end, d_b, in, out, unit, upper, st); break;
+        default: launch_sweep<64>(t->m, t->d_begin, t->d_end, d_b, in, out, unit, upper, st); break;
+        }
+    }
     for (const TrsvLaunch &l : t->launches) {
         if (l.chain) {
             auto kernel = t->chain_width == kVectorBlock ? trsv_chain<1> : t->chain_width == 2 * kVectorBlock ? trsv_chain<2> : trsv_chain<4>;
@@ -434,7 +588,7 @@ extern "C" int smvp_trsv_info(const smvp_trsv_t *t, smvp_trsv_info_t *out)
                           out->struct_size, sizeof(smvp_trsv_info_t));
     out->levels = t->sched.levels;
     out->max_level_width = t->sched.max_level_width;
-    out->launches = (int)t->launches.size();
+    out->launches = t->sweeps < 0 ? (int)t->launches.size() : t->m.rows > 0 ? t->sweeps + 1 : 0;
     out->chains = t->chains;
     out->chain_width = t->chain_width;
     out->missing_diagonals = t->sched.missing_diagonals;

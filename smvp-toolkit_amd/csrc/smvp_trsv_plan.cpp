@@ -88,6 +88,39 @@ void trsv_launches(const std::vector<int> &level_ptr, int chain_width, std::vect
     }
 }
 
+// K21: the storage range [begin_i, end_i) of every row -- the smallest that holds all of the row's entries inside the triangle and,
+// for DIAG_STORED, on the diagonal; [row_ptr[i], row_ptr[i]) where the row has none.  Everything of the row outside the range is of
+// the skipped kind, so a walk of the range alone adds the same values in the same order as a walk of the row.  Rows with ascending
+// columns get a tight range (nothing skipped inside it); an unsorted row a loose one, which is still right.  col_ind was checked by
+// trsv_analyse.
+void trsv_ranges(int rows, const int *row_ptr, const int *col_ind, int uplo, int diag, std::vector<int> *begin, std::vector<int> *end,
+                 long long *entries, int *longest)
+{
+    const bool upper = uplo == SMVP_TRSV_UPPER, unit = diag == SMVP_TRSV_DIAG_UNIT;
+    begin->assign((size_t)rows, 0);
+    end->assign((size_t)rows, 0);
+    *entries = 0;
+    *longest = 0;
+    for (int i = 0; i < rows; ++i) {
+        int a = row_ptr[i], z = row_ptr[i];
+        bool any = false;
+        for (int p = row_ptr[i]; p < row_ptr[i + 1]; ++p) {
+            const int c = col_ind[p];
+            if (c == i ? !unit : (upper ? c > i : c < i)) {
+                if (!any)
+                    a = p;
+                any = true;
+                z = p + 1;
+            }
+        }
+        (*begin)[(size_t)i] = a;
+        (*end)[(size_t)i] = z;
+        *entries += z - a;
+        if (z - a > *longest)
+            *longest = z - a;
+    }
+}
+
 }  // namespace smvp
 
 extern "C" int smvp_csr_trsv_levels(int rows, const int *row_ptr, const int *col_ind, int uplo, int *level_of_row, int *levels)

@@ -181,6 +181,7 @@ EXPORTS = [
     "smvp_csr_diagonal", "smvp_tjds_diagonal", "smvp_csr_pcg", "smvp_tjds_pcg", "smvp_csr_cg_multi", "smvp_tjds_cg_multi",
     "smvp_bicgstab_opts_default", "smvp_csr_bicgstab", "smvp_tjds_bicgstab",
     "smvp_csr_trsv_create", "smvp_trsv_solve", "smvp_trsv_info", "smvp_trsv_schedule", "smvp_trsv_destroy", "smvp_csr_trsv_levels",
+    "smvp_csr_trsv_create_sweeps", "smvp_trsv_sweeps",
     "smvp_csr_pcg_tri", "smvp_tjds_pcg_tri",
     "smvp_csr_pbicgstab", "smvp_tjds_pbicgstab",
     "smvp_gmres_opts_default", "smvp_csr_gmres", "smvp_tjds_gmres",
@@ -260,6 +261,8 @@ def lib():
         L.smvp_trsv_destroy.argtypes = [vp]
         L.smvp_trsv_destroy.restype = None
         L.smvp_csr_trsv_levels.argtypes = [ci, vp, vp, ci, vp, C.POINTER(ci)]
+        L.smvp_csr_trsv_create_sweeps.argtypes = [C.POINTER(vp), vp, ci, ci, ci, vp]
+        L.smvp_trsv_sweeps.argtypes = [vp, C.POINTER(ci)]
         L.smvp_csr_pcg_tri.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
         L.smvp_tjds_pcg_tri.argtypes = [vp, C.POINTER(CgOpts), vp, vp, vp, vp, vp, vp, C.POINTER(PcgResult), vp, vp, vp, vp]
         L.smvp_csr_pbicgstab.argtypes = [vp, C.POINTER(BicgstabOpts), vp, vp, vp, vp, vp, vp, C.POINTER(BicgstabResult), vp, vp, vp]
@@ -775,12 +778,24 @@ def trsv_levels(rows, row_ptr, col_ind, uplo):
 
 class TrsvPlan:
     """A triangular solve on a CsrMatrix (smvp_trsv_t, K15): T x = b for the `uplo` triangle of the matrix as stored.  It borrows
-    the matrix's device arrays and keeps a reference to the CsrMatrix."""
+    the matrix's device arrays and keeps a reference to the CsrMatrix.  sweeps=None is the exact, level-scheduled solve; an int is
+    that many Jacobi sweeps on the triangular system instead (smvp_csr_trsv_create_sweeps, K21), exact from levels - 1 sweeps on."""
 
-    def __init__(self, matrix, uplo, diag=TRSV_DIAG_STORED, stream=None):
+    def __init__(self, matrix, uplo, diag=TRSV_DIAG_STORED, stream=None, sweeps=None):
         self._t = C.c_void_p()
         self.matrix, self.rows, self.uplo, self.diag = matrix, matrix.rows, int(uplo), int(diag)
-        _check(lib().smvp_csr_trsv_create(C.byref(self._t), matrix._h, int(uplo), int(diag), _stream_ptr(stream)), "smvp_csr_trsv_create")
+        if sweeps is None:
+            _check(lib().smvp_csr_trsv_create(C.byref(self._t), matrix._h, int(uplo), int(diag), _stream_ptr(stream)), "smvp_csr_trsv_create")
+        else:
+            _check(lib().smvp_csr_trsv_create_sweeps(C.byref(self._t), matrix._h, int(uplo), int(diag), int(sweeps), _stream_ptr(stream)),
+                   "smvp_csr_trsv_create_sweeps")
+
+    @property
+    def sweeps(self):
+        """None for an exact plan, else the number of Jacobi sweeps a solve makes (smvp_trsv_sweeps)."""
+        n = C.c_int()
+        _check(lib().smvp_trsv_sweeps(self._t, C.byref(n)), "smvp_trsv_sweeps")
+        return None if n.value < 0 else n.value
 
     def solve(self, b, x, stream=None):
         """x = T^-1 b, asynchronous on `stream`: b and x are contiguous float64 CUDA tensors of `rows` elements; x may be b
@@ -942,10 +957,11 @@ class Ilu0:
         _check(lib().smvp_ilu0_info(self._f, C.byref(i)), "smvp_ilu0_info")
         return {name: getattr(i, name) for name, _ in Ilu0Info._fields_[1:]}
 
-    def plans(self, stream=None):
-        """(first, second) for pcg_tri with m=None: the LOWER / DIAG_UNIT and the UPPER / DIAG_STORED TrsvPlan of `matrix`.
-        Close them before this object."""
-        return (self.matrix.trsv_plan(TRSV_LOWER, TRSV_DIAG_UNIT, stream), self.matrix.trsv_plan(TRSV_UPPER, TRSV_DIAG_STORED, stream))
+    def plans(self, stream=None, sweeps=None):
+        """(first, second) for pcg_tri with m=None: the LOWER / DIAG_UNIT and the UPPER / DIAG_STORED TrsvPlan of `matrix`, exact
+        or, with an int, of that many Jacobi sweeps each.  Close them before this object."""
+        return (self.matrix.trsv_plan(TRSV_LOWER, TRSV_DIAG_UNIT, stream, sweeps),
+                self.matrix.trsv_plan(TRSV_UPPER, TRSV_DIAG_STORED, stream, sweeps))
 
     def close(self):
         if self._f:
@@ -1059,10 +1075,11 @@ class CsrMatrix:
         that hold NaN beyond a column's filled elements.  The product is spmm()'s: the kernel set_kernel chose plays no part."""
         return _cg_multi("smvp_csr_cg_multi", self._h, self.rows, B, X, m, X0, max_steps, tol, check_every, stream)
 
-    def trsv_plan(self, uplo, diag=TRSV_DIAG_STORED, stream=None):
+    def trsv_plan(self, uplo, diag=TRSV_DIAG_STORED, stream=None, sweeps=None):
         """A TrsvPlan for the `uplo` triangle of this matrix as stored (smvp_csr_trsv_create, K15): TRSV_LOWER or TRSV_UPPER,
-        the diagonal as stored or taken as ones.  Analysed on the host once; close the plan before the matrix."""
-        return TrsvPlan(self, uplo, diag, stream)
+        the diagonal as stored or taken as ones.  Analysed on the host once; close the plan before the matrix.  sweeps=None is
+        the exact solve; an int makes the plan that many Jacobi sweeps instead (smvp_csr_trsv_create_sweeps, K21)."""
+        return TrsvPlan(self, uplo, diag, stream, sweeps)
 
     def pcg_tri(self, b, x, first, second, m=None, x0=None, max_steps=100, tol=1e-10, check_every=10, stream=None):
         """Conjugate gradients for A x = b preconditioned with M = T1 diag(m)^-1 T2 (smvp_csr_pcg_tri, K16): z = M^-1 r is
