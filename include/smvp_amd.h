@@ -1302,6 +1302,112 @@ int smvp_tjds_gmres(smvp_tjds_t *h, const smvp_gmres_opts_t *opts, const double 
                     smvp_trsv_t *first, const double *d_m, smvp_trsv_t *second, smvp_gmres_result_t *result, double *rr_each,
                     double *restart_each, void *stream);
 
+/* ------------------------------------------------- LSQR: least squares for a rectangular matrix */
+/* min |A x - b|_2 for ANY M x N handle -- tall, wide, square, rank deficient -- by LSQR (Paige and Saunders), kernel K22 (new: the
+ * reference only multiplies).  It is the one solver here that takes rows != cols, and the loop around the transposed product
+ * above: a step is one product with A and one with A^T.  For a consistent system it returns a solution (from x_0 = 0 the one of
+ * least norm), else a least-squares solution.  `dot` is K12's, unchanged; sqrt is the correctly rounded IEEE root (as in K19);
+ * every other operation is one correctly rounded IEEE operation, on an element or on a scalar, with no FMA.  Every bracket below
+ * is one rounded operation.
+ * The bidiagonalisation's vectors are stored UNNORMALISED: uh_k = beta_k u_k (M doubles) and vh_k = alpha_k v_k (N doubles); each
+ * scaling is folded into the next pass that reads the vector, and no pass exists only to divide a vector by its norm.
+ *   bnorm = sqrt(dot(b, b))          thr = tol * bnorm
+ *   x = d_x0, or zeros if NULL;      uh_1 = b - A x_0    (d_x0 == NULL: uh_1 = b bit for bit, no product)
+ *   beta_1 = sqrt(dot(uh_1, uh_1))
+ *   p = A^T uh_1;   vh_1[i] = p[i] / beta_1;   alpha_1 = sqrt(dot(vh_1, vh_1))
+ *       (beta_1 zero, NaN or +-Inf: vh_1 is not formed and alpha_1 = +0.0)
+ *   phibar_1 = beta_1;  rhobar_1 = alpha_1;  A2 = alpha_1 * alpha_1;  anorm_0 = sqrt(A2);  rnorm_0 = beta_1;
+ *   arnorm_0 = beta_1 * alpha_1                                        -> rnorm_each[0], arnorm_each[0]
+ *   step 0 rules:  NONFINITE if bnorm, beta_1, alpha_1, anorm_0 or arnorm_0 is NaN or +-Inf;  CONVERGED if beta_1 <= thr;
+ *                  LEAST_SQUARES if alpha_1 == 0                       -> x = x_0, steps = updates = 0
+ *   w_1[i] = vh_1[i] / alpha_1
+ *   step k = 1, 2, ...:
+ *     q = A vh_k                     the handle's own product, bit for bit
+ *     uh_{k+1}[i] = (q[i] / alpha_k) - (alpha_k * (uh_k[i] / beta_k));          beta_{k+1} = sqrt(dot(uh_{k+1}, uh_{k+1}))
+ *     p = A^T uh_{k+1}               ht's own product (CSR), smvp_tjds_spmv_transposed (TJDS), bit for bit
+ *     vh_{k+1}[i] = (p[i] / beta_{k+1}) - (beta_{k+1} * (vh_k[i] / alpha_k));   alpha_{k+1} = sqrt(dot(vh_{k+1}, vh_{k+1}))
+ *         (beta_{k+1} zero, NaN or +-Inf: vh_{k+1} is not formed and alpha_{k+1} = +0.0)
+ *     rho = sqrt((rhobar_k * rhobar_k) + (beta_{k+1} * beta_{k+1}));   c = rhobar_k / rho;   s = beta_{k+1} / rho
+ *     theta = s * alpha_{k+1};   rhobar_{k+1} = -(c * alpha_{k+1});   phi = c * phibar_k;   phibar_{k+1} = s * phibar_k
+ *     tx = phi / rho;   tw = theta / rho
+ *     A2 = (A2 + (beta_{k+1} * beta_{k+1})) + (alpha_{k+1} * alpha_{k+1});   anorm_k = sqrt(A2)
+ *     ac = alpha_{k+1} * |c|;   rnorm_k = phibar_{k+1};   arnorm_k = phibar_{k+1} * ac
+ *     rule N:  NONFINITE if beta_{k+1}, alpha_{k+1}, rho, tx, tw, anorm_k, rnorm_k or arnorm_k is NaN or +-Inf
+ *                                     -> x stays x_{k-1}, updates = k - 1; rnorm, arnorm, anorm and A2 stay step k - 1's
+ *     x_k[i] = x_{k-1}[i] + (tx * w_k[i])                              rnorm_k, arnorm_k -> rnorm_each[k], arnorm_each[k]
+ *     rule S (first that holds):  CONVERGED if rnorm_k <= thr;  LEAST_SQUARES if ac <= atol * anorm_k;  MAX_STEPS if k == max_steps
+ *                                     -> x = x_k, updates = k
+ *     w_{k+1}[i] = (vh_{k+1}[i] / alpha_{k+1}) - (tw * w_k[i])
+ * rnorm is the recurrence's estimate phibar of |b - A x|, arnorm its estimate of |A^T (b - A x)|, anorm the running estimate of
+ * |A|_F: NORMS, not squares, because this method takes roots anyway.  CONVERGED is the residual rule |r| <= tol |b|;
+ * LEAST_SQUARES is the normal-equations rule |A^T r| <= atol |A|_F |r|, with |r| cancelled on both sides.
+ * Two ends that are no breakdown, and in which no quotient by zero is consumed.  beta_{k+1} == 0: the Krylov space is exhausted
+ * and the system is solved; alpha_{k+1} = +0.0, s = 0, c = +-1, rnorm_k = 0, the step completes its update of x and ends as
+ * CONVERGED, for every tol.  alpha_{k+1} == 0 with beta_{k+1} > 0: A^T uh_{k+1} = 0, x_k is a least-squares solution; ac = 0, the
+ * step completes its update and ends as LEAST_SQUARES, for every atol, unless it converged; at step 0 this is b orthogonal to
+ * range(A), and x_0 stands.  No scaling is done against overflow of the squares: that case shows as NONFINITE.
+ * The device evaluates the rules at EVERY step; once one has fired nothing more is written to x or to the histories.  The host
+ * reads a status block at looked steps only -- step 0, every k with k % check_every == 0, and k == max_steps -- and only to
+ * leave the loop: no result, history element or bit of d_x depends on check_every or on the stream.  No kernel waits on a
+ * value another workgroup writes; no atomics, no flags; every scalar hand-off is a launch boundary.
+ * That ht holds A^T is the caller's contract, as symmetry is for K12, and is not checked beyond its shape.
+ * Out of scope: damping (Tikhonov's lambda), the acond and xnorm estimates and a conlim rule, LSMR and CGLS, preconditioning,
+ * several right-hand sides, the sharded handles, and a CSR route that builds its own A^T (the library makes no hidden second
+ * copy: smvp_csr_create_transposed is the caller's call). */
+enum { SMVP_LSQR_CONVERGED = 0, SMVP_LSQR_LEAST_SQUARES = 1, SMVP_LSQR_MAX_STEPS = 2, SMVP_LSQR_NONFINITE = 3 };
+typedef struct smvp_lsqr_opts {
+    unsigned struct_size; /* set by smvp_lsqr_opts_default, checked as for smvp_cg_opts_t */
+    int max_steps;        /* >= 1; default 100 */
+    int check_every;      /* >= 1; default 10 */
+    int pad;
+    double tol;           /* >= 0, finite; default 1e-10: CONVERGED at |r| <= tol |b| */
+    double atol;          /* >= 0, finite; default 1e-10: LEAST_SQUARES at |A^T r| <= atol |A|_F |r| */
+} smvp_lsqr_opts_t;
+void smvp_lsqr_opts_default(smvp_lsqr_opts_t *o);
+typedef struct smvp_lsqr_result {
+    int steps;     /* steps done: pairs of products (those for uh_1 and vh_1 are not counted) */
+    int updates;   /* updates of x done: steps, or steps - 1 after rule N */
+    int reason;    /* SMVP_LSQR_* */
+    int pad;
+    double rnorm;  /* rnorm_updates */
+    double arnorm; /* arnorm_updates */
+    double anorm;  /* anorm_updates */
+    double bnorm;  /* sqrt(dot(b, b)) */
+} smvp_lsqr_result_t;
+/*   - h is M x N.  smvp_csr_lsqr: ht is the caller's handle of A^T, normally smvp_csr_create_transposed(h): REQUIRED, plain CSR,
+ *     N x M, h's nnz, on h's device.  q = A vh is smvp_csr_spmv(h) on h's current plan, p = A^T uh is smvp_csr_spmv(ht) on ht's
+ *     own; both plans may be any SMVP_CSR_KERNEL_* and are left as they are.  smvp_tjds_lsqr: one handle and no second copy;
+ *     q = A vh is smvp_tjds_set_x + smvp_tjds_spmv in the current mode, p = A^T uh is smvp_tjds_spmv_transposed (K8).
+ *   - d_b: M doubles.  d_x0: N doubles, NULL = zeros.  d_x: N doubles; the iterates live in it, and it holds x_updates afterwards.
+ *     d_x may be the same pointer as d_x0; any other overlap of the two, and any overlap of d_b and d_x, is SMVP_ERR_INVALID.
+ *     d_b is only read.  After SMVP_ERR_HIP the content of d_x is unspecified.
+ *   - rnorm_each, arnorm_each: caller-owned HOST arrays of max_steps + 1 doubles each, filled 0 .. updates.  Either may be NULL.
+ *     Both come from a device-side history copied back once at the end, and are left untouched beyond the filled elements.
+ *   - The call returns after the work on `stream` has finished.  It allocates its workspace per call -- uh and q (M doubles each),
+ *     vh, p and w (N each), the partials of three dots, one word, the histories, two status blocks -- and frees it on every way out.
+ *   - Beside the two products a step is TWO launches and eleven passes over a vector.  Pass U, after q = A vh_k: every workgroup
+ *     folds the partials of dot(vh_k, vh_k) and closes step k - 1 (its scalars and rules; workgroup 0 writes the status block
+ *     and the histories), applies step k - 1's updates of x and w (vh, w, x read, w, x written: 5 passes over N) and writes
+ *     uh_{k+1} with the partials of its dot (q, uh read, uh written: 3 passes over M).  Pass V, after p = A^T uh_{k+1}: every
+ *     workgroup folds those partials to beta_{k+1} and writes vh_{k+1} with the partials of its dot (p, vh read, vh written:
+ *     3 passes over N).  A step's close thus rides in the next step's pass U.  At a looked step the close is launched on its own
+ *     (pass U without its uh half) so that the host can read its status block, and the next step's pass U has nothing to close:
+ *     a third launch at looked steps only, the same arithmetic either way.  Step 0 is four launches of its own, the fill or copy of x and one or two products.
+ *   - SMVP_ERR_INVALID for: a NULL handle, ht (CSR), opts, result or d_b (before any HIP call); a struct_size that is not this
+ *     library's; max_steps < 1, check_every < 1, tol or atol negative, NaN or infinite; an ht that is not N x M with h's nnz on
+ *     h's device; a NULL d_x with N > 0; the overlaps above; a capturing stream.  SMVP_ERR_UNSUPPORTED for: a CSR handle (h or ht)
+ *     that is not plain CSR or is a row block with first_row != 0; a TJDS handle in ATOMIC mode or with ref-quirks on, as for
+ *     every solver.  Nothing is enqueued then, d_x and *result are left untouched, and a capturing stream's capture stays valid.
+ *   - M == 0 or N == 0: SMVP_OK, steps 0, updates 0, reason SMVP_LSQR_CONVERGED, all four norms and element 0 of both
+ *     histories +0.0; with M == 0 < N, d_x holds x_0 (zeros without one).  d_b may not be NULL even then.
+ *   - State: both CSR handles' plans are untouched -- smvp_csr_spmv on h and on ht gives the bits it gave before.  A TJDS handle's
+ *     permuted operand is afterwards that of the last vh multiplied: call smvp_tjds_set_x again before the next smvp_tjds_spmv.
+ *     A handle is used by one stream at a time, as ever. */
+int smvp_csr_lsqr(smvp_csr_t *h, smvp_csr_t *ht, const smvp_lsqr_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                  smvp_lsqr_result_t *result, double *rnorm_each, double *arnorm_each, void *stream);
+int smvp_tjds_lsqr(smvp_tjds_t *h, const smvp_lsqr_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                   smvp_lsqr_result_t *result, double *rnorm_each, double *arnorm_each, void *stream);
+
 /* ------------------------------------------- several GPUs, one host process */
 /* New design (the reference is one CPU thread): the matrix is cut into `ngpus` row blocks balanced by entries
  * (smvp_partition_rows); GPU g holds block g -- cut again into `chunks` row chunks, each its own CSR / TJDS handle --

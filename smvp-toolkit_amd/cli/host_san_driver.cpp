@@ -1,8 +1,8 @@
 // host_san_driver.cpp -- exercises the host side of libsmvp_amd under sanitizers (make -C smvp-toolkit_amd host-san).
 //
-// Not part of the product: a test driver linked against the nine host translation units only (reader, converters,
-// report writer, cache, CISR export, synthetic generators, the triangular solves' analysis, the ILU(0) check and host loop, error
-// text -- no HIP), built with
+// Not part of the product: a test driver linked against the ten host translation units only (reader, converters,
+// report writer, cache, CISR export, synthetic generators, the triangular solves' analysis, the ILU(0) check and host loop, LSQR's
+// argument check, error text -- no HIP), built with
 // g++ -fsanitize=address,undefined and, for the parallel Matrix Market tokeniser, -fsanitize=thread (SURVEY 5,
 // "race detection / sanitizers": the reference has none, CMakeLists.txt:33-34 even comments -Wall out).
 // tests/test_host_sanitizers.py runs it over the reference's sample files, malformed inputs, crafted cache files.
@@ -304,6 +304,48 @@ static int run_synth(const std::string &tmp)
         printf("five refused ILU(0) calls: %d as expected\n", rc17);
         if (rc17 != 5 || dp != std::vector<int>{0, 3, 6} || f3 != want)
             ++g_bad, fprintf(stderr, "FAILED: a refused ILU(0) call wrote its outputs\n");
+    }
+    // ---- K22's host side (smvp_lsqr_args.cpp): the defaults, and what smvp_csr_lsqr / smvp_tjds_lsqr refuse before any HIP call, through
+    // the check both entry points make first (a block of zeros stands in for a handle: it is not looked at)
+    {
+        smvp_lsqr_opts_t ok;
+        smvp_lsqr_opts_default(&ok);
+        smvp_lsqr_opts_default(nullptr);
+        if (ok.struct_size != sizeof ok || ok.max_steps != 100 || ok.check_every != 10 || ok.tol != 1e-10 || ok.atol != 1e-10)
+            ++g_bad, fprintf(stderr, "FAILED: the LSQR defaults\n");
+        const std::vector<char> fake(64, 0);
+        const void *h = fake.data(), *ht = fake.data() + 32;
+        smvp_lsqr_result_t res;
+        const double b = 1.0;
+        for (const char *fn : {"smvp_csr_lsqr", "smvp_tjds_lsqr"}) {
+            const bool csr = fn[5] == 'c';
+            MUST(smvp::lsqr_check_args(fn, h, csr ? ht : nullptr, csr, &ok, &res, &b));
+            int refused = smvp::lsqr_check_args(fn, nullptr, ht, csr, &ok, &res, &b) == SMVP_ERR_INVALID;
+            refused += smvp::lsqr_check_args(fn, h, nullptr, true, &ok, &res, &b) == SMVP_ERR_INVALID;
+            refused += smvp::lsqr_check_args(fn, h, ht, csr, nullptr, &res, &b) == SMVP_ERR_INVALID;
+            refused += smvp::lsqr_check_args(fn, h, ht, csr, &ok, nullptr, &b) == SMVP_ERR_INVALID;
+            refused += smvp::lsqr_check_args(fn, h, ht, csr, &ok, &res, nullptr) == SMVP_ERR_INVALID;
+            const double nan = std::strtod("nan", nullptr), inf = std::strtod("inf", nullptr);
+            for (int which = 0; which < 10; ++which) {
+                smvp_lsqr_opts_t o = ok;
+                switch (which) {
+                case 0: o.struct_size = 0; break;
+                case 1: o.struct_size = sizeof o - 8; break;
+                case 2: o.max_steps = 0; break;
+                case 3: o.check_every = 0; break;
+                case 4: o.tol = -1e-300; break;
+                case 5: o.tol = nan; break;
+                case 6: o.tol = inf; break;
+                case 7: o.atol = -1e-300; break;
+                case 8: o.atol = nan; break;
+                default: o.atol = inf; break;
+                }
+                refused += smvp::lsqr_check_args(fn, h, ht, csr, &o, &res, &b) == SMVP_ERR_INVALID;
+            }
+            printf("%s: %d of 15 bad argument lists refused\n", fn, refused);
+            if (refused != 15)
+                ++g_bad;
+        }
     }
     printf("version %s\n", smvp_version_string());
     return 0;

@@ -1,10 +1,10 @@
-// smvp_cg_common.h -- what the Krylov loops on a handle share (smvp_cg.hip: K12, K14, K16; smvp_bicgstab.hip: K13, K18; smvp_gmres.hip: K19): the
+// smvp_cg_common.h -- what the Krylov loops on a handle share (smvp_cg.hip: K12, K14, K16; smvp_bicgstab.hip: K13, K18; smvp_gmres.hip: K19; smvp_lsqr.hip: K22): the
 // order-defined dot's building blocks as include/smvp_amd.h words them, the grid rule of every vector pass, the finite test, the two
 // kernels both families launch, the checks every call makes before it touches the device, and the host side of a status loop around
-// the holder of a call's workspace.  Everything lives in an unnamed namespace: each of the three files compiles its own copy, device
+// the holder of a call's workspace.  Everything lives in an unnamed namespace: each of the four files compiles its own copy, device
 // code included.
 //
-// The launch discipline, for every solver of the three files (K19 ping-pongs its status block by writer, not by step parity).  No launch reads a word that another lane of the same launch writes, and
+// The launch discipline, for every solver of the four files (K19 ping-pongs its status block by writer, not by step parity; K22's closing launch reads the block before the one it writes).  No launch reads a word that another lane of the same launch writes, and
 // every hand-off between workgroups is a launch boundary: every dot has partials of its own, written by one launch and folded by
 // every workgroup of a later one (at most 2048 doubles, from L2), and a scalar that one launch folds reaches the later launches of
 // the step through a word of its own, written by workgroup 0 with a plain store.  NO KERNEL WAITS ON A VALUE ANOTHER WORKGROUP

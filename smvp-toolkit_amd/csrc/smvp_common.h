@@ -37,6 +37,11 @@ void trsv_ranges(int rows, const int *row_ptr, const int *col_ind, int uplo, int
 // K17, what an ILU(0) asks of a CSR pattern (smvp_ilu0_plan.cpp): smvp_csr_ilu0_check under the caller's name `fn`, the arguments
 // checked for null already
 int ilu0_check(const char *fn, int rows, const int *row_ptr, const int *col_ind, int *diag_pos, int *bad_row);
+
+// K22, what smvp_csr_lsqr (needs_ht) and smvp_tjds_lsqr refuse before any HIP call (smvp_lsqr_args.cpp): a NULL handle, ht, opts,
+// result or d_b, a struct_size that is not this library's, options out of range
+int lsqr_check_args(const char *fn, const void *h, const void *ht, bool needs_ht, const smvp_lsqr_opts_t *opts, const void *result,
+                    const double *d_b);
 }  // namespace smvp
 
 // internal, device side (smvp_convert_device.hip): see its definition

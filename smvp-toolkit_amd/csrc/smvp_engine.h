@@ -240,4 +240,11 @@ int gmres_run(const char *fn, int device, int rows, int cols, const smvp_gmres_o
               double *d_x, const KrylovPrecond &M, smvp_gmres_result_t *result, double *rr_each, double *restart_each, void *stream,
               const HandleProduct &product);
 
+// LSQR (K22, smvp_lsqr.hip), two products a step: forward is y = A x (cols -> rows elements), transposed y = A^T x (rows -> cols).
+// The handle files make smvp_common.h's lsqr_check_args and their own checks of the handles first; lsqr_run checks the operands and
+// the stream, then allocates, iterates and frees.  rows != cols is what it is for.
+int lsqr_run(const char *fn, int device, int rows, int cols, const smvp_lsqr_opts_t *opts, const double *d_b, const double *d_x0,
+             double *d_x, smvp_lsqr_result_t *result, double *rnorm_each, double *arnorm_each, void *stream, const HandleProduct &forward,
+             const HandleProduct &transposed);
+
 }  // namespace smvp

@@ -1007,8 +1007,8 @@ extern "C" int smvp_csr_spmv(smvp_csr_t *h, const double *d_x, double *d_y, void
     return smvp::csr_spmv_stamped(h, d_x, d_y, stream, nullptr);
 }
 
-// What the solvers on a CSR handle (K11 to K14, K16, K18, K19; the steps are smvp_power.hip's, smvp_cg.hip's, smvp_bicgstab.hip's and
-// smvp_gmres.hip's) share: the
+// What the solvers on a CSR handle (K11 to K14, K16, K18, K19, K22; the steps are smvp_power.hip's, smvp_cg.hip's, smvp_bicgstab.hip's,
+// smvp_gmres.hip's and smvp_lsqr.hip's) share: the
 // product is smvp_csr_spmv's on the current plan, which it leaves as it is, and a handle that belongs to a TJDS matrix is refused.
 static smvp::HandleProduct csr_product(smvp_csr_t *h, void *stream)
 {
@@ -1126,6 +1126,28 @@ extern "C" int smvp_csr_gmres(smvp_csr_t *h, const smvp_gmres_opts_t *opts, cons
         return rc;
     return smvp::gmres_run("smvp_csr_gmres", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, smvp::KrylovPrecond{first, d_m, second}, result,
                            rr_each, restart_each, stream, csr_product(h, stream));
+}
+
+// K22: h is M x N, ht the caller's handle of A^T; each multiplies on its own current plan, which it keeps
+extern "C" int smvp_csr_lsqr(smvp_csr_t *h, smvp_csr_t *ht, const smvp_lsqr_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                             smvp_lsqr_result_t *result, double *rnorm_each, double *arnorm_each, void *stream)
+{
+    const char *fn = "smvp_csr_lsqr";
+    if (int rc = smvp::lsqr_check_args(fn, h, ht, true, opts, result, d_b))
+        return rc;
+    for (const smvp_csr_t *a : {(const smvp_csr_t *)h, (const smvp_csr_t *)ht}) {
+        if (int rc = refuse_tjds_flavor(fn, a))
+            return rc;
+        if (a->row0 != 0)
+            return smvp::fail(SMVP_ERR_UNSUPPORTED, "%s: %s is a row block (first_row = %lld): whole matrices only", fn, a == h ? "h" : "ht", a->row0);
+    }
+    if (ht->rows != h->cols || ht->cols != h->rows || ht->nnz != h->nnz)
+        return smvp::fail(SMVP_ERR_INVALID, "%s: ht is %d x %d with %d entries, the transpose of h (%d x %d, %d entries) is not", fn, ht->rows,
+                          ht->cols, ht->nnz, h->rows, h->cols, h->nnz);
+    if (ht->device != h->device)
+        return smvp::fail(SMVP_ERR_INVALID, "%s: ht lives on device %d, h on device %d", fn, ht->device, h->device);
+    return smvp::lsqr_run(fn, h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rnorm_each, arnorm_each, stream, csr_product(h, stream),
+                          csr_product(ht, stream));
 }
 
 // the owner kernel, whose launch can time itself on the device?

@@ -383,7 +383,7 @@ extern "C" int smvp_tjds_spmv(smvp_tjds_t *h, double *d_y, void *stream)
     return smvp::tjds_spmv_stamped(h, d_y, stream, nullptr);
 }
 
-// What the solvers on a TJDS handle (K11 to K14, K16, K18, K19) share: the product is smvp_tjds_set_x + smvp_tjds_spmv in the current mode,
+// What the solvers on a TJDS handle (K11 to K14, K16, K18, K19, K22) share: the product is smvp_tjds_set_x + smvp_tjds_spmv in the current mode,
 // which has to be one that overwrites y and gives the same bits on every run.  The steps are smvp_power.hip's, smvp_cg.hip's and
 // smvp_bicgstab.hip's; the solves of K16 and K18 are the caller's plans' (on CSR handles of their own: a TJDS handle has no
 // triangular solve; Jacobi needs none).
@@ -499,6 +499,19 @@ extern "C" int smvp_tjds_gmres(smvp_tjds_t *h, const smvp_gmres_opts_t *opts, co
         return rc;
     return smvp::gmres_run("smvp_tjds_gmres", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, smvp::KrylovPrecond{first, d_m, second}, result,
                            rr_each, restart_each, stream, tjds_product(h, stream));
+}
+
+// K22: the one handle gives both products, A v in the current mode and A^T u by K8 from the same arrays
+extern "C" int smvp_tjds_lsqr(smvp_tjds_t *h, const smvp_lsqr_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
+                              smvp_lsqr_result_t *result, double *rnorm_each, double *arnorm_each, void *stream)
+{
+    if (int rc = smvp::lsqr_check_args("smvp_tjds_lsqr", h, nullptr, false, opts, result, d_b))
+        return rc;
+    if (int rc = refuse_unless_overwrites_y("smvp_tjds_lsqr", h))
+        return rc;
+    return smvp::lsqr_run("smvp_tjds_lsqr", h->device, h->rows, h->cols, opts, d_b, d_x0, d_x, result, rnorm_each, arnorm_each, stream,
+                          tjds_product(h, stream),
+                          [h, stream](const double *x, double *y) { return smvp_tjds_spmv_transposed(h, x, y, stream); });
 }
 
 // the row-gather product (which overwrites y) through the owner kernel of `rg`, on the operand of smvp_tjds_set_x

@@ -125,6 +125,16 @@ class GmresResult(C.Structure):
     _fields_ = [("steps", C.c_int), ("cycles", C.c_int), ("columns", C.c_int), ("reason", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
 
 
+class LsqrOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("max_steps", C.c_int), ("check_every", C.c_int), ("pad", C.c_int), ("tol", C.c_double),
+                ("atol", C.c_double)]
+
+
+class LsqrResult(C.Structure):
+    _fields_ = [("steps", C.c_int), ("updates", C.c_int), ("reason", C.c_int), ("pad", C.c_int), ("rnorm", C.c_double),
+                ("arnorm", C.c_double), ("anorm", C.c_double), ("bnorm", C.c_double)]
+
+
 class TrsvInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("levels", C.c_int), ("max_level_width", C.c_int), ("launches", C.c_int), ("chains", C.c_int),
                 ("chain_width", C.c_int), ("missing_diagonals", C.c_int), ("lanes_per_row", C.c_int), ("entries", C.c_longlong),
@@ -143,6 +153,7 @@ TRSV_DIAG_STORED, TRSV_DIAG_UNIT = 0, 1
 CG_CONVERGED, CG_MAX_STEPS, CG_BREAKDOWN, CG_NONFINITE = 0, 1, 2, 3
 BICGSTAB_CONVERGED, BICGSTAB_MAX_STEPS, BICGSTAB_BREAKDOWN, BICGSTAB_NONFINITE = 0, 1, 2, 3
 GMRES_CONVERGED, GMRES_MAX_STEPS, GMRES_BREAKDOWN, GMRES_NONFINITE = 0, 1, 2, 3
+LSQR_CONVERGED, LSQR_LEAST_SQUARES, LSQR_MAX_STEPS, LSQR_NONFINITE = 0, 1, 2, 3
 GATHER_NONE, GATHER_OVERLAPPED, GATHER_AFTER = 0, 1, 2
 EXCHANGE_RCCL, EXCHANGE_COPIES, EXCHANGE_DIRECT, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGE_NAMES = {EXCHANGE_RCCL: "rccl", EXCHANGE_COPIES: "copies", EXCHANGE_DIRECT: "direct", EXCHANGE_AUTO: "auto"}
@@ -185,6 +196,7 @@ EXPORTS = [
     "smvp_csr_pcg_tri", "smvp_tjds_pcg_tri",
     "smvp_csr_pbicgstab", "smvp_tjds_pbicgstab",
     "smvp_gmres_opts_default", "smvp_csr_gmres", "smvp_tjds_gmres",
+    "smvp_lsqr_opts_default", "smvp_csr_lsqr", "smvp_tjds_lsqr",
     "smvp_csr_ilu0_create", "smvp_ilu0_factor", "smvp_ilu0_matrix", "smvp_ilu0_info", "smvp_ilu0_destroy", "smvp_csr_ilu0_check",
     "smvp_csr_ilu0_host",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
@@ -271,6 +283,10 @@ def lib():
         L.smvp_gmres_opts_default.restype = None
         L.smvp_csr_gmres.argtypes = [vp, C.POINTER(GmresOpts), vp, vp, vp, vp, vp, vp, C.POINTER(GmresResult), vp, vp, vp]
         L.smvp_tjds_gmres.argtypes = [vp, C.POINTER(GmresOpts), vp, vp, vp, vp, vp, vp, C.POINTER(GmresResult), vp, vp, vp]
+        L.smvp_lsqr_opts_default.argtypes = [C.POINTER(LsqrOpts)]
+        L.smvp_lsqr_opts_default.restype = None
+        L.smvp_csr_lsqr.argtypes = [vp, vp, C.POINTER(LsqrOpts), vp, vp, vp, C.POINTER(LsqrResult), vp, vp, vp]
+        L.smvp_tjds_lsqr.argtypes = [vp, C.POINTER(LsqrOpts), vp, vp, vp, C.POINTER(LsqrResult), vp, vp, vp]
         L.smvp_csr_ilu0_create.argtypes = [C.POINTER(vp), vp, vp]
         L.smvp_ilu0_factor.argtypes = [vp, vp]
         L.smvp_ilu0_matrix.argtypes = [vp, C.POINTER(vp)]
@@ -905,6 +921,25 @@ def _gmres(fn, handle, b, x, first, second, m, x0, restart, max_steps, tol, chec
     return r, rr[:filled], tr[:r.cycles]
 
 
+def lsqr_opts(max_steps=100, tol=1e-10, atol=1e-10, check_every=10):
+    """smvp_lsqr_opts_t from smvp_lsqr_opts_default with the four fields set."""
+    o = LsqrOpts()
+    lib().smvp_lsqr_opts_default(C.byref(o))
+    o.max_steps, o.check_every, o.tol, o.atol = int(max_steps), int(check_every), float(tol), float(atol)
+    return o
+
+
+def _lsqr(fn, handles, b, x, x0, max_steps, tol, atol, check_every, stream):
+    """smvp_csr_lsqr (handles = h, ht) / smvp_tjds_lsqr (handles = h,) -> (LsqrResult, rnorm_each, arnorm_each), the histories cut to
+    the result.updates + 1 filled elements."""
+    _device_vectors(b=b, x=x, x0=x0)
+    o = lsqr_opts(max_steps, tol, atol, check_every)
+    r = LsqrResult()
+    rn, arn = np.zeros(max(int(max_steps), 0) + 1), np.zeros(max(int(max_steps), 0) + 1)
+    _check(getattr(lib(), fn)(*handles, C.byref(o), _dev_ptr(b), _dev_ptr(x0), _dev_ptr(x), C.byref(r), _p(rn), _p(arn), _stream_ptr(stream)), fn)
+    return r, rn[:r.updates + 1], arn[:r.updates + 1]
+
+
 def ilu0_check(rows, row_ptr, col_ind):
     """diag_pos, the position of every row's (i, i), for CSR arrays on the host that admit an ILU(0) (smvp_csr_ilu0_check, K17):
     every row's columns strictly ascending, a stored diagonal in every row.  Raises SmvpError otherwise; its bad_row attribute is the
@@ -1111,6 +1146,23 @@ class CsrMatrix:
         Nothing depends on check_every but how often the host waits."""
         return _gmres("smvp_csr_gmres", self._h, b, x, first, second, m, x0, restart, max_steps, tol, check_every, stream)
 
+    def lsqr(self, b, x, at=None, x0=None, max_steps=100, tol=1e-10, atol=1e-10, check_every=10, stream=None):
+        """LSQR for min |A x - b| on any rows x cols matrix (smvp_csr_lsqr, K22): b holds rows elements, x and x0 cols; x0 = None
+        starts from zeros, and x may be x0.  at is a CsrMatrix of A^T, cols x rows -- transposed() makes one, and a caller who
+        solves more than once keeps it; at = None builds transposed() for this call and closes it afterwards.  Each matrix
+        multiplies on its own current kernel.  Returns (LsqrResult, rnorm_each, arnorm_each) after the work on `stream` has
+        finished: the estimates of |b - A x| and |A^T (b - A x)| after every update of x, element 0 for x0.  reason is
+        LSQR_CONVERGED (|r| <= tol |b|), LSQR_LEAST_SQUARES (|A^T r| <= atol |A|_F |r|), LSQR_MAX_STEPS or LSQR_NONFINITE.
+        Nothing depends on check_every but how often the host waits."""
+        if at is not None and not isinstance(at, CsrMatrix):
+            raise ValueError("at must be a CsrMatrix or None, not %s" % type(at).__name__)
+        own = self.transposed(stream) if at is None else None
+        try:
+            return _lsqr("smvp_csr_lsqr", (self._h, (own or at)._h), b, x, x0, max_steps, tol, atol, check_every, stream)
+        finally:
+            if own is not None:
+                own.close()
+
     def spmm(self, X, Y, stream=None):
         """Y = A X for k vectors at once (smvp_csr_spmm): X (cols x k) and Y (rows x k) are float64 CUDA tensors with
         stride(1) == 1, ldx = X.stride(0), ldy = Y.stride(0).  Every column of Y is the serial loop's bits.  Asynchronous on
@@ -1241,6 +1293,12 @@ class TjdsMatrix:
         K19; ROW_GATHER or TWO_PHASE, no ref-quirks): operands and result as CsrMatrix.gmres.  The plans belong to CsrMatrix
         handles; afterwards the handle's permuted operand is the last vector multiplied: call set_x again."""
         return _gmres("smvp_tjds_gmres", self._h, b, x, first, second, m, x0, restart, max_steps, tol, check_every, stream)
+
+    def lsqr(self, b, x, x0=None, max_steps=100, tol=1e-10, atol=1e-10, check_every=10, stream=None):
+        """LSQR for min |A x - b| on this handle alone (smvp_tjds_lsqr, K22): A v is the product of the current mode (ROW_GATHER or
+        TWO_PHASE, no ref-quirks), A^T u is spmv_transposed, from the same arrays.  Operands and result as CsrMatrix.lsqr.  Call
+        set_x again before the next spmv."""
+        return _lsqr("smvp_tjds_lsqr", (self._h,), b, x, x0, max_steps, tol, atol, check_every, stream)
 
     def spmv_transposed(self, x, y, stream=None):
         """y = A^T x from the TJDS arrays themselves (smvp_tjds_spmv_transposed, K8): x of `rows`, y of `cols` float64 CUDA
