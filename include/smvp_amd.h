@@ -171,13 +171,15 @@ int smvp_device_count(int *count);
 int smvp_device_info(int device, char *name, size_t name_cap, int *compute_units,
                      size_t *hbm_bytes);
 
-/* CSR kernel families (smvp_csr_set_kernel).  AUTO picks STREAM; STREAM_CARRY when some row is longer
+/* CSR kernel families (smvp_csr_set_kernel).  AUTO picks STREAM; STREAM_PACKED instead where STREAM would run 2048-entry tiles
+ * with 16-bit offsets, one product moves more than 1 GiB and at most 55 % of the values are not among the matrix's 64 most
+ * frequent ones (counted exactly when the plan is built); STREAM_CARRY when some row is longer
  * than 16384 entries; COLSWEEP for a large matrix whose gathers scatter over an operand much larger than
  * the L2 (measured at create time on samples of col_ind: spread >= 0.6, rows long enough for the sweep's
  * window); BINNED for a large matrix of which a good share (>= 10 %) of the entries lies far from the
  * diagonal and scatters (spread >= 0.2) -- SURVEY 8(d)'s memplus-shaped random model.  Every family gives
  * the same result from run to run, bit for bit.
- * COLSWEEP, BINNED, the 16-bit column offsets of STREAM and the TJDS value cache keep (parts of) the entries a
+ * COLSWEEP, BINNED, STREAM_PACKED, the 16-bit column offsets of STREAM and the TJDS value cache keep (parts of) the entries a
  * second time, copied when the plan is built: a handle over adopted device arrays (SMVP_MEM_DEVICE) whose
  * val / col_ind are then changed in place must be re-planned (smvp_csr_set_kernel) or re-created.  (smvp_csr_spmm keeps no
  * second copy: its plan depends on row_ptr alone, and it reads val / col_ind themselves.)  A handle made by
@@ -185,7 +187,8 @@ int smvp_device_info(int device, char *name, size_t name_cap, int *compute_units
  * Family by family, for val changed in place (tests/test_gpu_adopted.py holds every sentence):
  *   VECTOR, STREAM, STREAM_CARRY   read val itself: the next smvp_csr_spmv multiplies the new values, without any call (STREAM's
  *                                  second copy is of columns only);
- *   COLSWEEP, BINNED               keep a copy of the values: call smvp_csr_set_kernel (the same kernel and param will do) first;
+ *   COLSWEEP, BINNED,              keep a copy of the values: call smvp_csr_set_kernel (the same kernel and param will do) first;
+ *   STREAM_PACKED
  *   AUTO                           is one of the above: call smvp_csr_set_kernel(h, SMVP_CSR_KERNEL_AUTO, 0) unless
  *                                  smvp_csr_get_kernel names a family of the first line.
  * After col_ind changed in place call smvp_csr_set_kernel on every family (smvp_csr_spmm alone needs no call): the plan, its
@@ -224,7 +227,7 @@ enum {
                                          (workgroup b of a launch runs on XCD b % 8 and sweeps eighth b % 8 of the columns for
                                          the four whole strips of row group b / 8; the eight partial sums of a row meet in 8 *
                                          rows doubles of scratch and are added by a second kernel).  Never picked by AUTO */
-    SMVP_CSR_KERNEL_BINNED = 5        /* for matrices with a band around the diagonal plus many entries far from it
+    SMVP_CSR_KERNEL_BINNED = 5,       /* for matrices with a band around the diagonal plus many entries far from it
                                          (anywhere in an operand much larger than the L2): the entries are kept a second
                                          time, split by |column - row| > band.  The near part is summed out of a row
                                          block's window of x in LDS (rows of a block of 8192 sorted by length, every
@@ -239,6 +242,17 @@ enum {
                                          (ordered against the caller's stream by events); a handle is therefore used by
                                          one stream at a time, like every plan that keeps buffers.  param: the band
                                          (0 = 4096) */
+    SMVP_CSR_KERNEL_STREAM_PACKED = 6 /* STREAM at 2048-entry tiles with the values of the packable tiles -- the full tiles that read
+                                         16-bit offsets -- kept a second time in packed form: one byte per entry that indexes a
+                                         table of the matrix's 64 most frequent values (by bit pattern: -0.0 is not +0.0, a NaN
+                                         keeps its payload), and the values that are not in the table wavefront by wavefront.  A
+                                         product reads 1 + 2 + 8 * (share of such values) bytes per entry instead of 10; every
+                                         value it multiplies is the double val held when the plan was built and every row is summed
+                                         as STREAM sums it: y is bit-identical to STREAM's at 2048-entry tiles.  Wide tiles, the
+                                         last, partial tile and the entries a tile reads past its end read val itself.  For
+                                         circuit, stencil, graph and unit-weight matrices larger than the caches.  param: 0 or
+                                         2048.  Refused (SMVP_ERR_UNSUPPORTED, the handle goes back to STREAM) where the 16-bit
+                                         offsets are not in use.  The timed entry points run it as single stamped launches */
 };
 enum {
     SMVP_MEM_HOST = 0,  /* arrays are host memory: copied to the device */

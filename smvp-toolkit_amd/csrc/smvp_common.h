@@ -62,6 +62,12 @@ int build_tile_half_streams(const int *d_pos, int nnz, int tile, const int *d_st
                             int *runs_total, ihipStream_t *stream);
 int build_column_offsets(const int *d_col_ind, int nnz, int tile, int *d_col_base, unsigned short *d_col16, int *fits,
                          ihipStream_t *stream);
+// kFlavorCsr16P: the values of the packable tiles (full, d_col_base[tile] >= 0; 2048-entry tiles) a second time as codes and escapes.
+// Allocates the four arrays (the caller frees them; all null after a failure).  *doubles_read = the entries one product still reads
+// as 8-byte values: the escapes, counted exactly, and every entry of a tile that is not packable.  max_doubles >= 0: where that count
+// is larger, the build ends once it is known -- SMVP_OK, the count, and no array (the escapes are never allocated); < 0: no bound.
+int build_packed_values(const double *d_val, int nnz, const int *d_col_base, unsigned char **d_code8, double **d_hot, int **d_esc_ptr,
+                        double **d_esc_val, long long *doubles_read, long long *esc_slots, long long max_doubles, ihipStream_t *stream);
 int build_tile_overflow(const int *d_pos, const int *d_ovf_ptr, int total, int ntiles, int tile, int nnz,
                         const int *d_start_pos, int num_diag, const double *d_val, double *d_ovf_val, int *d_ovf_k, int positions,
                         ihipStream_t *stream);

@@ -1052,9 +1052,233 @@ __global__ __launch_bounds__(256) void column_offsets(const int *__restrict__ co
     }
 }
 
+// ---- kFlavorCsr16P: the packed values of the packable tiles (build_packed_values below)
+constexpr int kPackedTile = smvp::kCol16LaneOrderTile, kPackedVpt = kPackedTile / 256;
+constexpr int kPackedSampleMax = 1 << 20;
+
+// the bit patterns of every stride-th value, with a dummy payload for the pair sort
+__global__ __launch_bounds__(256) void sample_value_bits(const double *__restrict__ val, int nnz, int stride, int n, u64 *__restrict__ key,
+                                                         unsigned *__restrict__ idx)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        key[i] = (u64)__double_as_longlong(val[(long long)i * stride]);  // (i * stride < nnz: n = ceil(nnz / stride))
+        idx[i] = (unsigned)i;
+    }
+}
+
+// code of a bit pattern: its place in the table (`nhot` patterns, ascending) or the escape code
+__device__ __forceinline__ unsigned hot_code(const u64 *tab, int nhot, u64 bits)
+{
+    int lo = 0, hi = nhot;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (tab[mid] < bits)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo < nhot && tab[lo] == bits ? (unsigned)lo : (unsigned)smvp::kEscapeCode;
+}
+
+// how many of a wavefront's escapes the lanes below this one hold, and how many it holds in all: entry k's share is a count over the
+// wavefront's mask for entry k -- the very sum the tile kernel forms, so both put a lane's escapes at the same places
+__device__ __forceinline__ void escape_places(const unsigned (&code)[kPackedVpt], int *before, int *total)
+{
+    int b = 0, n = 0;
+#pragma unroll
+    for (int k = 0; k < kPackedVpt; ++k) {
+        const u64 mask = __ballot(code[k] == (unsigned)smvp::kEscapeCode);
+        b = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, (unsigned)b));
+        n += __popcll(mask);
+    }
+    *before = b, *total = n;
+}
+
+// One workgroup per tile, thread t = thread t of the tile kernel.  A packable tile: the lane's 8 codes as one 8-byte store at its
+// col16_slot places, the wavefront's escape count rounded up to even into run_len.  Any other tile: four empty runs, and all its
+// entries counted as read from val.  (code8 of a tile that is not packable is never written and never read.)
+__global__ __launch_bounds__(256) void packed_codes(const double *__restrict__ val, int nnz, const int *__restrict__ col_base,
+                                                    const u64 *__restrict__ hot_bits, int nhot, unsigned char *__restrict__ code8,
+                                                    int *__restrict__ run_len, u64 *__restrict__ doubles_read)
+{
+    __shared__ u64 tab[smvp::kHotValues];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const long long s = (long long)b * kPackedTile;
+    if (col_base[b] < 0 || s + kPackedTile > (long long)nnz) {  // (uniform)
+        if (t < 4)
+            run_len[4 * b + t] = 0;
+        if (t == 0)
+            atomicAdd(doubles_read, (u64)((long long)nnz - s < kPackedTile ? (long long)nnz - s : kPackedTile));
+        return;
+    }
+    if (t < smvp::kHotValues)
+        tab[t] = t < nhot ? hot_bits[t] : 0;
+    __syncthreads();
+    unsigned code[kPackedVpt];
+#pragma unroll
+    for (int k = 0; k < kPackedVpt; ++k)
+        code[k] = hot_code(tab, nhot, (u64)__double_as_longlong(val[s + smvp::tile_lane_entry(t, k, kPackedVpt)]));
+    uint2 w = make_uint2(0, 0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        w.x |= code[k] << (8 * k), w.y |= code[k + 4] << (8 * k);
+    *reinterpret_cast<uint2 *>(code8 + s + (t >> 6) * (64 * kPackedVpt) + (t & 63) * kPackedVpt) = w;
+    int before, total;
+    escape_places(code, &before, &total);
+    if ((t & 63) == 0) {
+        run_len[4 * b + (t >> 6)] = (total + 1) & ~1;
+        atomicAdd(doubles_read, (u64)total);
+    }
+}
+
+// The same grid once esc_ptr holds the runs' starts: every escape's value to its place (tile, wavefront, lane, k), a zero into the
+// padding slot of a run of odd length, and the four words of a tile that is not packable complemented (the kernel's mark).
+__global__ __launch_bounds__(256) void packed_escapes(const double *__restrict__ val, int nnz, const int *__restrict__ col_base,
+                                                      const unsigned char *__restrict__ code8, int *__restrict__ esc_ptr,
+                                                      double *__restrict__ esc_val)
+{
+    const int b = blockIdx.x, t = threadIdx.x;
+    const long long s = (long long)b * kPackedTile;
+    if (col_base[b] < 0 || s + kPackedTile > (long long)nnz) {
+        if (t < 4)
+            esc_ptr[4 * b + t] = ~esc_ptr[4 * b + t];  // (nobody else reads these four words in this launch)
+        return;
+    }
+    const uint2 w = *reinterpret_cast<const uint2 *>(code8 + s + (t >> 6) * (64 * kPackedVpt) + (t & 63) * kPackedVpt);
+    unsigned code[kPackedVpt];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        code[k] = (w.x >> (8 * k)) & 0xffu, code[k + 4] = (w.y >> (8 * k)) & 0xffu;
+    int before, total;
+    escape_places(code, &before, &total);
+    const int start = esc_ptr[4 * b + (t >> 6)];
+    int at = start + before;
+#pragma unroll
+    for (int k = 0; k < kPackedVpt; ++k)
+        if (code[k] == (unsigned)smvp::kEscapeCode)
+            esc_val[at++] = val[s + smvp::tile_lane_entry(t, k, kPackedVpt)];
+    if ((t & 63) == 0 && (total & 1))
+        esc_val[start + total] = 0.0;
+}
+
 }  // namespace
 
 namespace smvp {
+
+int build_packed_values(const double *d_val, int nnz, const int *d_col_base, unsigned char **d_code8, double **d_hot, int **d_esc_ptr,
+                        double **d_esc_val, long long *doubles_read, long long *esc_slots, long long max_doubles, hipStream_t st)
+{
+    *d_code8 = nullptr, *d_hot = nullptr, *d_esc_ptr = nullptr, *d_esc_val = nullptr;
+    *doubles_read = nnz, *esc_slots = 0;
+    if (nnz <= 0)
+        return fail(SMVP_ERR_INVALID, "build_packed_values: no entries");
+    const int ntiles = (int)(((long long)nnz + kPackedTile - 1) / kPackedTile);
+    Scratch sc;
+    // ---- the hot table: the most frequent bit patterns of a sample of at most 2^20 values taken at a fixed stride.  The sample is
+    // sorted on the device; its runs are counted and the kHotValues longest chosen here (ties: the smaller pattern), a few
+    // milliseconds once per plan.  The table need not be the best one: what it covers is counted exactly below.
+    const int stride = (int)(((long long)nnz + kPackedSampleMax - 1) / kPackedSampleMax);
+    const int n = (int)(((long long)nnz + stride - 1) / stride);
+    u64 *k0, *k1;
+    unsigned *i0, *i1;
+    HIP_TRY(sc.get(&k0, (size_t)n));
+    HIP_TRY(sc.get(&k1, (size_t)n));
+    HIP_TRY(sc.get(&i0, (size_t)n));
+    HIP_TRY(sc.get(&i1, (size_t)n));
+    hipLaunchKernelGGL(sample_value_bits, dim3(blocks_for(n)), dim3(256), 0, st, d_val, nnz, stride, n, k0, i0);
+    HIP_TRY(hipGetLastError());
+    {
+        size_t tmp_bytes = 0;
+        HIP_TRY(prim::radix_sort_pairs(nullptr, tmp_bytes, k0, k1, i0, i1, (size_t)n, 0u, 64u, st));
+        char *tmp;
+        HIP_TRY(sc.get(&tmp, tmp_bytes));
+        HIP_TRY(prim::radix_sort_pairs(tmp, tmp_bytes, k0, k1, i0, i1, (size_t)n, 0u, 64u, st));
+    }
+    std::vector<u64> sorted((size_t)n);
+    HIP_TRY(hipMemcpyAsync(sorted.data(), k1, sizeof(u64) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<std::pair<int, u64>> runs;  // {length, pattern}
+    for (size_t i = 0; i < sorted.size();) {
+        size_t j = i + 1;
+        while (j < sorted.size() && sorted[j] == sorted[i])
+            ++j;
+        runs.push_back({(int)(j - i), sorted[i]});
+        i = j;
+    }
+    const size_t nhot = std::min<size_t>(runs.size(), (size_t)kHotValues);
+    std::partial_sort(runs.begin(), runs.begin() + (std::ptrdiff_t)nhot, runs.end(),
+                      [](const std::pair<int, u64> &a, const std::pair<int, u64> &b) { return a.first != b.first ? a.first > b.first : a.second < b.second; });
+    u64 hot_bits[kHotValues] = {};  // ascending by pattern (the code is the place); slots from nhot on are zero and never referenced
+    for (size_t i = 0; i < nhot; ++i)
+        hot_bits[i] = runs[i].second;
+    std::sort(hot_bits, hot_bits + nhot);
+
+    // ---- the codes, the runs' lengths, their starts, the escapes
+    unsigned char *code8 = nullptr;
+    double *hot = nullptr, *esc_val = nullptr;
+    int *esc_ptr = nullptr;
+    auto release = [&]() {
+        for (void *p : {(void *)code8, (void *)hot, (void *)esc_ptr, (void *)esc_val})
+            if (p)
+                (void)hipFree(p);
+    };
+    if (hipMalloc((void **)&code8, (size_t)nnz + 8) != hipSuccess || hipMalloc((void **)&hot, sizeof hot_bits) != hipSuccess ||
+        hipMalloc((void **)&esc_ptr, ((size_t)4 * ntiles + 4) * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        release();
+        return fail(SMVP_ERR_ALLOC, "cannot allocate the packed values (%d entries)", nnz);
+    }
+    int rc = SMVP_OK;
+    auto tried = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == SMVP_OK)
+            rc = fail(SMVP_ERR_HIP, "build_packed_values: %s failed: %s", what, hipGetErrorString(e));
+        return rc == SMVP_OK;
+    };
+    u64 *count = nullptr;
+    u64 h_count = 0;
+    int h_slots = 0;
+    char *scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+    (void)prim::exclusive_scan(nullptr, scan_bytes, esc_ptr, esc_ptr, 0, (size_t)4 * ntiles + 1, st);
+    if (tried(sc.get(&count, 1), "hipMalloc") && tried(sc.get(&scan_tmp, scan_bytes), "hipMalloc") &&
+        tried(hipMemcpyAsync(hot, hot_bits, sizeof hot_bits, hipMemcpyHostToDevice, st), "hipMemcpyAsync") &&
+        tried(hipMemsetAsync(count, 0, sizeof(u64), st), "hipMemsetAsync") &&
+        tried(hipMemsetAsync(esc_ptr + (size_t)4 * ntiles, 0, sizeof(int), st), "hipMemsetAsync")) {
+        hipLaunchKernelGGL(packed_codes, dim3((unsigned)ntiles), dim3(256), 0, st, d_val, nnz, d_col_base, reinterpret_cast<const u64 *>(hot),
+                           (int)nhot, code8, esc_ptr, count);
+        if (tried(hipGetLastError(), "packed_codes") &&
+            tried(prim::exclusive_scan(scan_tmp, scan_bytes, esc_ptr, esc_ptr, 0, (size_t)4 * ntiles + 1, st), "exclusive_scan") &&
+            tried(hipMemcpyAsync(&h_slots, esc_ptr + (size_t)4 * ntiles, sizeof(int), hipMemcpyDeviceToHost, st), "hipMemcpyAsync") &&
+            tried(hipMemcpyAsync(&h_count, count, sizeof(u64), hipMemcpyDeviceToHost, st), "hipMemcpyAsync"))
+            (void)tried(hipStreamSynchronize(st), "hipStreamSynchronize");
+    }
+    if (rc == SMVP_OK && max_doubles >= 0 && (long long)h_count > max_doubles) {
+        // the caller's bound is passed and the count is exact: nothing more is built (the escapes, up to 8 bytes per entry and a
+        // second pass over val, are never allocated), the arrays stay null and the count goes back
+        release();
+        *doubles_read = (long long)h_count;
+        return SMVP_OK;
+    }
+    if (rc == SMVP_OK) {
+        // (two slots past the last run: the widest load of the kernel, a pair, ends inside the allocation wherever it starts)
+        if (hipMalloc((void **)&esc_val, ((size_t)h_slots + 4) * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(SMVP_ERR_ALLOC, "cannot allocate the packed values' escapes (%d values)", h_slots);
+        } else if (tried(hipMemsetAsync(esc_val + h_slots, 0, 4 * sizeof(double), st), "hipMemsetAsync")) {
+            hipLaunchKernelGGL(packed_escapes, dim3((unsigned)ntiles), dim3(256), 0, st, d_val, nnz, d_col_base, code8, esc_ptr, esc_val);
+            if (tried(hipGetLastError(), "packed_escapes"))
+                (void)tried(hipStreamSynchronize(st), "hipStreamSynchronize");
+        }
+    }
+    if (rc != SMVP_OK) {
+        release();
+        return rc;
+    }
+    *d_code8 = code8, *d_hot = hot, *d_esc_ptr = esc_ptr, *d_esc_val = esc_val;
+    *doubles_read = (long long)h_count, *esc_slots = h_slots;
+    return SMVP_OK;
+}
 
 // kFlavorCsr16: col_ind a second time as 16-bit offsets from every tile's smallest column, for the tiles whose columns span
 // less than 65536 (d_col_base[tile] = -1 marks the others: they read col_ind itself).  *fits when at least half of the

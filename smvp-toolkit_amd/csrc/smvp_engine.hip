@@ -77,6 +77,15 @@ struct TilePlan {
     // STREAM, plain CSR: the single launches read val and the 16-bit offsets of full tiles with the read-once hint (decided when
     // the plan is built: kReadOnceMinBytes or plan option "csr_read_once")
     int read_once = 0;
+    // STREAM_PACKED (csr_stream_owner<8, kFlavorCsr16P, .>): the values of the packable tiles -- full, with 16-bit offsets -- a second
+    // time: a code per entry in smvp::col16_slot order, the table of the 64 most frequent bit patterns the codes index, the
+    // start of every wavefront's run of escapes (4 * ntiles + 1) and the escapes themselves; smvp::build_packed_values.
+    // packed_doubles: entries a product still reads as 8-byte values (escapes, and the entries of tiles that are not packable).
+    unsigned char *d_code8 = nullptr;
+    double *d_hot = nullptr, *d_esc_val = nullptr;
+    int *d_esc_ptr = nullptr;
+    long long packed_doubles = 0, esc_slots = 0;
+    int packed_bounded = 0;  // (set by AUTO for the build it asks for: stop at the count where the share is over its bound)
 };
 
 // COLSWEEP: the entries a second time, every strip sorted by column (built on the device); build_sweep_plan
@@ -152,7 +161,8 @@ void free_tile_plan(TilePlan *p)
     for (void *q : {(void *)p->d_tile_row, (void *)p->d_tile_next, (void *)p->d_col16, (void *)p->d_col_base, (void *)p->d_row_rel,
                     (void *)p->d_carry_row, (void *)p->d_carry, (void *)p->d_pos_sorted, (void *)p->d_meta, (void *)p->d_ovf_ptr,
                     (void *)p->d_ovf_k, (void *)p->d_ovf_val, (void *)p->d_cache_ptr, (void *)p->d_val_cache, (void *)p->d_group_run,
-                    (void *)p->d_word32, (void *)p->d_run_ptr, (void *)p->d_run_tab})
+                    (void *)p->d_word32, (void *)p->d_run_ptr, (void *)p->d_run_tab, (void *)p->d_code8, (void *)p->d_hot, (void *)p->d_esc_ptr,
+                    (void *)p->d_esc_val})
         if (q)
             (void)hipFree(q);
     *p = TilePlan{};
@@ -187,10 +197,12 @@ void free_spmm_plan(SpmmPlan *p)
 
 // the derived quantities the plans are read through
 inline bool tile_ordered(int flavor) { return flavor == smvp::kFlavorTjdsS || flavor == smvp::kFlavorTjdsH; }
+inline bool stream_family(int k) { return k == SMVP_CSR_KERNEL_STREAM || k == SMVP_CSR_KERNEL_STREAM_PACKED; }  // the owner (tile) kernel
 inline bool runs_on_tile_plan(int k) { return k != SMVP_CSR_KERNEL_VECTOR && k != SMVP_CSR_KERNEL_COLSWEEP && k != SMVP_CSR_KERNEL_BINNED; }
 // what the owner kernel is launched with: `flavor`, but for plain CSR with 16-bit column offsets (try_column_offsets builds them
 // for plain CSR only, so for a TJDS flavour this is `flavor`)
-inline int owner_flavor(const smvp_csr *h) { return h->tile.d_col16 ? smvp::kFlavorCsr16 : h->flavor; }
+// (and with packed values, which build_tile_plan_parts builds for STREAM_PACKED only and only on top of the offsets)
+inline int owner_flavor(const smvp_csr *h) { return h->tile.d_code8 ? smvp::kFlavorCsr16P : h->tile.d_col16 ? smvp::kFlavorCsr16 : h->flavor; }
 inline double csr_matrix_bytes(const smvp_csr *h) { return 12.0 * h->nnz + 4.0 * (h->rows + 1.0); }
 // rows of one strip of the column sweep: a workgroup's kSweepWaves wavefronts share rb rows, or rb * parts where every strip is cut
 // into column parts (one wavefront each); XCD-private parts run on whole strips
@@ -439,7 +451,7 @@ bool binned_suits(smvp_csr *h)
 // handle without offsets.  An error where the two arrays cannot be allocated or their build fails.
 int try_column_offsets(smvp_csr *h)
 {
-    if (h->flavor != smvp::kFlavorCsr || h->kernel != SMVP_CSR_KERNEL_STREAM || h->vpt < 4 || h->nnz <= 0 ||
+    if (h->flavor != smvp::kFlavorCsr || !stream_family(h->kernel) || h->vpt < 4 || h->nnz <= 0 ||
         smvp::option("csr_col16", 1) == 0)  // (plan option: 0 keeps the 32-bit columns)
         return SMVP_OK;
     std::vector<int> tiles;
@@ -486,10 +498,36 @@ constexpr double kSweepAlternateMinBytes = 256.0 * 1024 * 1024;
 // Infinity Cache hold, wholly or in good part, is slower with the hint (profiles/col16_lane_order_measured.txt has the curve).
 constexpr double kReadOnceMinBytes = 1024.0 * 1024 * 1024;
 
-int build_tile_plan_parts(smvp_csr *h)
+// The packed family: AUTO picks it where it would have picked STREAM at 2048-entry tiles with the 16-bit offsets in use, one
+// product's algorithmic bytes exceed kReadOnceMinBytes (below that the caches hold the matrix and the decode cannot pay) and the
+// share of the entries that are still read as 8-byte values -- counted exactly when the plan is built -- is at most this.
+// Measured (profiles/packed_values_measured.txt, section 4: the headline's structure and pwt x459 with their values replaced, PACKED
+// against STREAM alternated in one process; gain on memplus x944 / pwt x459):
+//   share 0     +19.9 % / +20.5 %      0.5   +7.1 % / +8.5 %      0.6   +2.9 % / +4.0 %      0.7   -0.7 % / +1.9 %
+//         0.25  +14.9 % / +15.6 %      0.55  +4.0 % / +6.2 %      0.65  +1.3 % / +3.4 %      0.75  -1.4 % / -1.0 %     1   -13.8 % / -11.9 %
+// The blocks of STREAM itself spread by 0.1-0.3 % in most rows of that table and by 2.6-3.0 % in the two in which a block fell into
+// the headline's other mode: 0.55 is the largest share at which the family wins by more than the largest of those spreads on both.
+constexpr double kPackedMaxEscapeShare = 0.55;
+
+inline double tile_product_bytes(const smvp_csr *h) { return 12.0 * (double)h->nnz + 12.0 * h->rows + 8.0 * h->cols; }
+
+// STREAM_PACKED on top of a tile plan with 2048-entry tiles and 16-bit offsets.  bounded (AUTO's question): where more than
+// kPackedMaxEscapeShare of the entries would still be read as doubles the build stops at the count and the plan is left without
+// the arrays (SMVP_OK; TilePlan::d_code8 tells); the family set by name is built whatever the share.
+int attach_packed_values(smvp_csr *h, bool bounded)
+{
+    TilePlan &t = h->tile;
+    if (!t.d_col16 || h->vpt * smvp::kStreamBlock != smvp::kCol16LaneOrderTile)
+        return smvp::fail(SMVP_ERR_UNSUPPORTED, "the packed values need 2048-entry tiles whose columns fit 16-bit offsets: this matrix's do not");
+    return smvp::build_packed_values(h->d_val, h->nnz, t.d_col_base, &t.d_code8, &t.d_hot, &t.d_esc_ptr, &t.d_esc_val, &t.packed_doubles,
+                                     &t.esc_slots, bounded ? (long long)(kPackedMaxEscapeShare * (double)h->nnz) : -1ll, nullptr);
+}
+
+int build_tile_plan_parts(smvp_csr *h, bool packed_bounded)
 {
     TilePlan &t = h->tile;
     free_tile_plan(&t);
+    t.packed_bounded = packed_bounded;
     if (int rc = try_column_offsets(h))
         return rc;
     const int tile = smvp::kStreamBlock * h->vpt;
@@ -512,7 +550,7 @@ int build_tile_plan_parts(smvp_csr *h)
         tile_next[(size_t)b] = rp[tile_row[(size_t)b + 1]];
     if (int rc = upload(&t.d_tile_row, tile_row))
         return rc;
-    if (h->kernel == SMVP_CSR_KERNEL_STREAM) {
+    if (stream_family(h->kernel)) {
         if (int rc = upload(&t.d_tile_next, tile_next))
             return rc;
         if (h->rows > 0 && smvp::option("csr_rowrel", 1) != 0) {  // (plan option: 0 = keep row_ptr)
@@ -535,11 +573,14 @@ int build_tile_plan_parts(smvp_csr *h)
     // plan option: 0 = every product sweeps forward, 1 = the plain launches alternate whatever the size; default: they alternate
     // where one product's bytes do not fit the Infinity Cache anyway (see kSweepAlternateMinBytes)
     const int alternate = smvp::option("csr_sweep_alternate", -1);
-    const double product_bytes = 12.0 * (double)h->nnz + 12.0 * h->rows + 8.0 * h->cols;
+    const double product_bytes = tile_product_bytes(h);
     t.sweep_alternate = alternate < 0 ? product_bytes > kSweepAlternateMinBytes : alternate != 0;
     // plan option: 0 / 1 = the single launches' val and col16 loads never / always carry the read-once hint; default: by size
     const int read_once = smvp::option("csr_read_once", -1);
     t.read_once = h->flavor != smvp::kFlavorCsr ? 0 : read_once < 0 ? product_bytes > kReadOnceMinBytes : read_once != 0;
+    if (h->kernel == SMVP_CSR_KERNEL_STREAM_PACKED)
+        if (int rc = attach_packed_values(h, t.packed_bounded != 0))
+            return rc;
     if (tile_ordered(h->flavor)) {
         // every tile's entries in TJDS order + what each tile reads past its end, in row order
         std::vector<int> ovf_ptr((size_t)ntiles + 1, 0);
@@ -578,9 +619,9 @@ int build_tile_plan_parts(smvp_csr *h)
 }
 
 // A build that fails leaves the handle without a tile plan (smvp_csr_spmv then refuses it), never with the arrays built so far.
-int build_tile_plan(smvp_csr *h)
+int build_tile_plan(smvp_csr *h, bool packed_bounded = false)
 {
-    const int rc = build_tile_plan_parts(h);
+    const int rc = build_tile_plan_parts(h, packed_bounded);
     if (rc != SMVP_OK)
         free_tile_plan(&h->tile);
     return rc;
@@ -615,6 +656,8 @@ bool choose_csr_kernel(smvp_csr *h, int kernel, int param)
         return false;
     if (kernel == SMVP_CSR_KERNEL_STREAM_CARRY && param != 0 && param != 1024 && param != 2048)
         return false;
+    if (kernel == SMVP_CSR_KERNEL_STREAM_PACKED && param != 0 && param != smvp::kCol16LaneOrderTile)
+        return false;
     if (kernel == SMVP_CSR_KERNEL_COLSWEEP && !sweep_param_ok(param))
         return false;
     if (kernel == SMVP_CSR_KERNEL_BINNED && param < 0)
@@ -625,6 +668,8 @@ bool choose_csr_kernel(smvp_csr *h, int kernel, int param)
     if (kernel == SMVP_CSR_KERNEL_VECTOR) {
         h->lanes_per_row = param > 0 ? param : pow2_at_least(mean);
     } else {
+        if (kernel == SMVP_CSR_KERNEL_STREAM_PACKED)
+            param = smvp::kCol16LaneOrderTile;  // the one tile size the family has: the plan keeps it like one the caller named
         int tile = param > 0 ? param : 0;
         h->tile_chosen = param > 0;
         if (tile == 0) {  // 1024 measured 1-4 % ahead of 2048 on memplus x944 and pwt x459; 256-entry tiles when
@@ -637,6 +682,35 @@ bool choose_csr_kernel(smvp_csr *h, int kernel, int param)
         h->vpt = tile / smvp::kStreamBlock;
     }
     return true;
+}
+
+// AUTO has resolved to STREAM and the tile plan stands: does the packed family take over (kPackedMaxEscapeShare has the rule)?
+// Plan option "csr_packed": 0 = never; 1 = wherever the tiles allow and whatever the size (the plan moves to 2048-entry tiles
+// for it), the escape share still decides; default: by the rule.  Memory that runs out, or tiles that do not suit, leave the
+// handle on STREAM; only a tile plan that cannot be rebuilt is an error.
+int auto_packed_values(smvp_csr *h)
+{
+    const int wanted = smvp::option("csr_packed", -1);
+    if (wanted == 0 || h->flavor != smvp::kFlavorCsr || h->plain_only || h->nnz <= 0)
+        return SMVP_OK;
+    const bool tiles_suit = h->tile.d_col16 && h->vpt * smvp::kStreamBlock == smvp::kCol16LaneOrderTile;
+    if (wanted < 0 && !(tiles_suit && tile_product_bytes(h) > kReadOnceMinBytes))
+        return SMVP_OK;
+    // (either way the build is the bounded one: it ends at the exact count where the share is over the bound, the arrays are
+    // there only where the family pays)
+    if (tiles_suit) {
+        if (attach_packed_values(h, true) == SMVP_OK && h->tile.d_code8)
+            h->kernel = SMVP_CSR_KERNEL_STREAM_PACKED;
+        else
+            (void)hipGetLastError();  // (a failed build leaves no array: the handle stays on STREAM, its plan as it stands)
+        return SMVP_OK;
+    }
+    choose_csr_kernel(h, SMVP_CSR_KERNEL_STREAM_PACKED, 0);
+    if (build_tile_plan(h, true) == SMVP_OK && h->tile.d_code8)
+        return SMVP_OK;
+    (void)hipGetLastError();
+    choose_csr_kernel(h, SMVP_CSR_KERNEL_STREAM, 0);
+    return build_tile_plan(h);
 }
 
 }  // namespace
@@ -681,7 +755,7 @@ static int build_binned(smvp_csr *h, int band)
 static int plan_csr(smvp_csr *h, int kernel, int param, bool silent_fallback)
 {
     if (!choose_csr_kernel(h, kernel, param))
-        return smvp::fail(SMVP_ERR_INVALID, "entries per tile must be 256 (stream only), 1024 or 2048 for the kernel "
+        return smvp::fail(SMVP_ERR_INVALID, "entries per tile must be 256 (stream only), 1024 or 2048 (stream-packed: 2048) for the kernel "
                                             "this matrix resolves to (column sweep: 256 ... 20480 rows per block, a multiple of 4; binned: the near band, >= 0)");
     const double t0 = wall_ms();
     free_sweep_plan(&h->sweep);
@@ -689,6 +763,17 @@ static int plan_csr(smvp_csr *h, int kernel, int param, bool silent_fallback)
     int rc = SMVP_OK;
     if (runs_on_tile_plan(h->kernel)) {
         rc = build_tile_plan(h);
+        if (rc == SMVP_OK && kernel == SMVP_CSR_KERNEL_AUTO && h->kernel == SMVP_CSR_KERNEL_STREAM)
+            rc = auto_packed_values(h);
+        if (rc != SMVP_OK && h->kernel == SMVP_CSR_KERNEL_STREAM_PACKED) {
+            // the family was asked for by name and the matrix's tiles do not suit it, or its arrays do not fit: back to STREAM,
+            // like the two other plans that keep a copy of the values
+            const std::string why = smvp_last_error();
+            (void)hipGetLastError();
+            choose_csr_kernel(h, SMVP_CSR_KERNEL_STREAM, 0);
+            const int tile_rc = build_tile_plan(h);
+            rc = silent_fallback ? tile_rc : smvp::fail(rc, "%s", why.c_str());
+        }
     } else {
         free_tile_plan(&h->tile);
         if (h->kernel != SMVP_CSR_KERNEL_VECTOR)
@@ -841,7 +926,7 @@ extern "C" int smvp_csr_set_kernel(smvp_csr_t *h, int kernel, int param)
         return smvp::fail(SMVP_ERR_INVALID, "null handle");
     if (h->flavor != smvp::kFlavorCsr && kernel != SMVP_CSR_KERNEL_STREAM)
         return smvp::fail(SMVP_ERR_UNSUPPORTED, "this matrix flavour runs on the stream kernel only");
-    if (kernel < SMVP_CSR_KERNEL_AUTO || kernel > SMVP_CSR_KERNEL_BINNED)
+    if (kernel < SMVP_CSR_KERNEL_AUTO || kernel > SMVP_CSR_KERNEL_STREAM_PACKED)
         return smvp::fail(SMVP_ERR_INVALID, "unknown CSR kernel %d", kernel);
     if (kernel == SMVP_CSR_KERNEL_VECTOR && param != 0 &&
         (param < 2 || param > 64 || (param & (param - 1)) != 0))
@@ -894,6 +979,7 @@ static int fill_owner_launch(const smvp_csr_t *h, const double *d_x, double *d_y
     l.stamps = stamps;
     l.rows = h->rows, l.nnz = h->nnz, l.ntiles = h->tile.ntiles;
     l.col16 = h->tile.d_col16, l.col_base = h->tile.d_col_base;
+    l.code8 = h->tile.d_code8, l.hot = h->tile.d_hot, l.esc_ptr = h->tile.d_esc_ptr, l.esc_val = h->tile.d_esc_val;
     l.row_rel = h->tile.d_row_rel;
     l.read_once = h->tile.read_once;
     l.unit_x = h->src.unit_operand ? 1 : 0;
@@ -904,7 +990,7 @@ static int fill_owner_launch(const smvp_csr_t *h, const double *d_x, double *d_y
 // csr_repeat_grid.  The products are those of csr_spmv_stamped, bit for bit: the same kernel body walks the same tiles.
 int smvp::csr_repeat_grid(const smvp_csr_t *h)
 {
-    if (!h || h->kernel != SMVP_CSR_KERNEL_STREAM || !h->tile.d_tile_row || h->rows <= 0)
+    if (!h || h->kernel != SMVP_CSR_KERNEL_STREAM || !h->tile.d_tile_row || h->rows <= 0)  // (STREAM_PACKED has no repeating form)
         return 0;
     DeviceScope on(h->device);
     return smvp::owner_repeat_grid(h->vpt, owner_flavor(h), h->tile.ntiles);
@@ -987,7 +1073,7 @@ int smvp::csr_spmv_stamped(smvp_csr_t *h, const double *d_x, double *d_y, void *
                                       sweep_strip_rows(h->sweep), h->sweep.parts, h->sweep.per_launch, h->sweep.g, h->sweep.d_part, st);
     else if (h->kernel == SMVP_CSR_KERNEL_VECTOR)
         e = smvp::launch_csr_vector(h->lanes_per_row, h->d_row_ptr, h->d_col_ind, h->d_val, d_x, d_y, h->rows, st);
-    else if (h->kernel == SMVP_CSR_KERNEL_STREAM) {
+    else if (stream_family(h->kernel)) {
         smvp::OwnerLaunch l{};
         if (int rc = fill_owner_launch(h, d_x, d_y, stamps, &l))
             return rc;
@@ -1153,7 +1239,7 @@ extern "C" int smvp_csr_lsqr(smvp_csr_t *h, smvp_csr_t *ht, const smvp_lsqr_opts
 // the owner kernel, whose launch can time itself on the device?
 int smvp::csr_stamp_slots(const smvp_csr_t *h)
 {
-    return h && h->kernel == SMVP_CSR_KERNEL_STREAM && h->tile.d_tile_row ? smvp::owner_stamp_slots(h->tile.ntiles, h->flavor) : 0;
+    return h && stream_family(h->kernel) && h->tile.d_tile_row ? smvp::owner_stamp_slots(h->tile.ntiles, h->flavor) : 0;
 }
 
 std::string smvp::csr_owner_kernel_name(const smvp_csr_t *h)
@@ -1183,7 +1269,7 @@ extern "C" int smvp_csr_describe(const smvp_csr_t *h, char *kernel_name, size_t 
                 snprintf(kernel_name, cap, "csr_colsweep<%d>", h->sweep.g);
         else if (h->kernel == SMVP_CSR_KERNEL_VECTOR)
             snprintf(kernel_name, cap, "csr_vector_rows<%d>", h->lanes_per_row);
-        else if (h->kernel == SMVP_CSR_KERNEL_STREAM)
+        else if (stream_family(h->kernel))
             snprintf(kernel_name, cap, "%s", smvp::csr_owner_kernel_name(h).c_str());
         else
             snprintf(kernel_name, cap, "csr_stream_tiles<%d>", h->vpt);
@@ -1235,6 +1321,8 @@ double smvp::csr_plan_bytes(const smvp_csr_t *h)
         b += 2.0 * n + 4.0 * (n / 1024 + 1);
     if (h->tile.d_row_rel)
         b += 2.0 * h->rows;
+    if (h->tile.d_code8)  // a code per entry, the hot table, four run starts per tile, the escapes (padded)
+        b += 1.0 * n + 8.0 * smvp::kHotValues + 4.0 * (4.0 * t + 1) + 8.0 * (double)h->tile.esc_slots;
     if (tile_ordered(h->flavor)) {
         b += 4.0 * (t + 1) + 12.0 * h->tile.ovf_total + 4.0 * (t + 2) + 8.0 * h->tile.cached_total;
         b += h->flavor == smvp::kFlavorTjdsH ? 4.0 * n + 4.0 * (t + 2) + 8.0 * h->tile.runs_total + 2.0 * (n / 32 + 1) : 8.0 * n;

@@ -37,6 +37,9 @@ Option g_options[] = {
     {"csr_col16", {-1}},        // 0: the CSR tile kernel keeps col_ind's 32-bit columns (default: 16-bit offsets where a tile's columns lie close)
     {"csr_rowrel", {-1}},       // 0: the tile kernel's second phase reads row_ptr (default: its own 16-bit row offsets)
     {"csr_read_once", {-1}},    // 0 / 1: the plain CSR tile kernel's single launches never / always read val and col16 with the read-once (non-temporal) hint (default: by size)
+    {"csr_packed", {-1}},       // AUTO alone reads it (smvp_csr_set_kernel with SMVP_CSR_KERNEL_STREAM_PACKED does not): 0 = AUTO never picks that family; 1 = it picks
+                                // it wherever the tiles allow, whatever the size (the escape share still decides); default: by the rule (2048-entry tiles with
+                                // 16-bit offsets, more than 1 GiB per product, the share)
     {"csr_sweep_alternate", {-1}},  // 0: every product of the tile kernel sweeps its tiles forward; 1: a handle's plain launches alternate forward / backward
                                     // whatever the size (default: they alternate where one product's bytes exceed the Infinity Cache)
     {"binned_near", {-1}},      // 1: the binned plan's near part runs on the tile kernel (default 0: csr_near_window where it suits)

@@ -78,7 +78,10 @@ constexpr int kFlavorTjdsS = 3;  // the same entries, every tile's in TJDS order
 constexpr int kFlavorTjdsH = 4;  // kFlavorTjdsS with a 16-bit second word: slot | run hint << 11; the start_pos of the entry's
                                  // diagonal comes from the tile's run table (6 bytes of index per entry instead of 8)
 constexpr int kFlavorCsr16 = 5;  // kFlavorCsr reading 16-bit column offsets: x[col_base[tile] + col16[j]] (tiles whose columns span < 65536)
+constexpr int kFlavorCsr16P = 6; // kFlavorCsr16 at 2048-entry tiles, the values of full narrow ("packable") tiles read as 1-byte codes into a table of
+                                 // the matrix's 64 most frequent bit patterns, the others (escapes) packed wavefront by wavefront (SMVP_CSR_KERNEL_STREAM_PACKED)
 constexpr int kSlotBits = 11;    // a tile holds at most 2048 entries
+                                 // (kHotValues, kEscapeCode: smvp_tile_map.h, beside col16_slot)
 
 struct OwnerLaunch {
     const int *row_ptr = nullptr, *col_ind = nullptr;
@@ -94,6 +97,13 @@ struct OwnerLaunch {
     const double *val_cache = nullptr;
     const unsigned short *col16 = nullptr;                               // kFlavorCsr16
     const int *col_base = nullptr;
+    // kFlavorCsr16P (build_packed_values): a code per entry of the packable tiles in smvp::col16_slot order, the hot table, the start
+    // of every wavefront's run of escapes (4 * ntiles + 1; ~start, negative, in the four words of a tile that is not packable) and
+    // the escapes' values in the order (tile, wavefront, lane, k), every run padded to an even count
+    const unsigned char *code8 = nullptr;
+    const double *hot = nullptr;
+    const int *esc_ptr = nullptr;
+    const double *esc_val = nullptr;
     const unsigned short *group_run = nullptr;        // kFlavorTjdsH
     const unsigned *word32 = nullptr;
     int unit_x = 0;                            // kFlavorTjdsH: the operand is the unit vector (second phase of the two-phase TJDS product)

@@ -227,9 +227,10 @@ hipError_t launch_csr_stream_owner(int vpt, int flavor, const OwnerLaunch &l, hi
     }
 #ifdef SMVP_PHASE_STAMPS   // (diagnostic builds keep every flavour here: one set of phase counters)
     SMVP_OWNER_CSR_FORMS(SMVP_OWNER)
+    SMVP_OWNER_CSR_PACKED_FORMS(SMVP_OWNER)
 #else
     // the CSR flavours are instantiated in smvp_owner_csr.hip, under the max-ILP scheduling strategy
-    if (flavor == kFlavorCsr || flavor == kFlavorCsr16)
+    if (flavor == kFlavorCsr || flavor == kFlavorCsr16 || flavor == kFlavorCsr16P)
         return launch_owner_csr(vpt, flavor, l, ex, grid.x, group, stream);
 #endif
     SMVP_OWNER_TJDS_FORMS(SMVP_OWNER)

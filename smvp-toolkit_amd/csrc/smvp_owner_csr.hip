@@ -1,5 +1,5 @@
-// smvp_owner_csr.hip -- the plain launches of the owner (tile) kernel's CSR flavours, kFlavorCsr and kFlavorCsr16, the read-once
-// forms included.  This file is compiled with the max-ILP scheduling strategy (the Makefile's ILPFLAGS), which is all that sets
+// smvp_owner_csr.hip -- the plain launches of the owner (tile) kernel's CSR flavours, kFlavorCsr, kFlavorCsr16 and (2048-entry tiles
+// only) kFlavorCsr16P, the read-once forms included.  This file is compiled with the max-ILP scheduling strategy (the Makefile's ILPFLAGS), which is all that sets
 // it apart from smvp_owner.hip: the kernel is the one of smvp_owner_kernel.h, and launch_csr_stream_owner there prepares `ex`,
 // grid and group.
 #include "smvp_owner_kernel.h"
@@ -27,8 +27,10 @@ hipError_t launch_owner_csr(int vpt, int flavor, const OwnerLaunch &l, const Own
 #define SMVP_OWNER_PLAIN(V, F) SMVP_OWNER(csr_stream_owner, V, F)
     if (l.read_once) {  // (the 256-entry tiles have no such form and take the plain one)
         SMVP_OWNER_CSR_WIDE_FORMS(SMVP_OWNER_ONCE)
+        SMVP_OWNER_CSR_PACKED_FORMS(SMVP_OWNER_ONCE)
     }
     SMVP_OWNER_CSR_FORMS(SMVP_OWNER_PLAIN)
+    SMVP_OWNER_CSR_PACKED_FORMS(SMVP_OWNER_PLAIN)
 #undef SMVP_OWNER_PLAIN
 #undef SMVP_OWNER_ONCE
 #undef SMVP_OWNER

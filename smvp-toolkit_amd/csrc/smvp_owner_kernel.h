@@ -62,6 +62,12 @@ namespace smvp {
 //                  (banded and block-structured matrices: all of them) the plan keeps col_ind a second time as 16-bit
 //                  offsets from the tile's smallest column; the tile adds its base (one scalar) back.  Wider tiles
 //                  (col_base < 0), overflow entries and the slow paths read col_ind itself.
+//   kFlavorCsr16P  kFlavorCsr16 at 2048-entry tiles with 1 + 2 + 8 * (escape share) instead of 10 bytes per entry: for the full narrow
+//                  ("packable") tiles the plan keeps val a second time as one byte per entry, in col16_slot order -- an index into
+//                  a table of the matrix's 64 most frequent bit patterns, or 255 -- and the values that are not in the table
+//                  (escapes) wavefront by wavefront in the order the lanes hold them.  Every value is the double val holds, bit for
+//                  bit, and every row is summed as kFlavorCsr16 sums it: y is bit-identical.  Wide tiles, the last partial tile,
+//                  overflow entries and the slow paths read val itself.  (SMVP_CSR_KERNEL_STREAM_PACKED)
 //   kFlavorTjdsK   TJDS by rows: the stream lists, row by row, the TJDS positions p of the row's entries (`pos`) and
 //                  their permuted columns k (`col_ind`): value val[p] gathered from the jagged-diagonal array,
 //                  operand x_perm[k] (the one-kernel TJDS product, see ensure_row_gather in the engine)
@@ -86,14 +92,18 @@ typedef double double2v __attribute__((ext_vector_type(2)));
 
 // The streams every flavour reads are plain __restrict__ kernel parameters (the compiler then keeps the uniform plan
 // reads on the scalar unit and is free to order the loads); what only some flavours need travels in this struct.
+// Csr16P's four arrays travel in the words of four that only the TJDS flavours read (a flavour is one or the other; PackedArrays
+// below is how the kernel reads them): the struct keeps its size, its fields and their types, so every other form of the kernel --
+// and the repeating kernel, whose control block follows this struct in the argument block -- is the code it was before the flavour
+// existed (as unions of two pointers the TjdsH forms already came out with other registers).
 struct OwnerExtra {
-    const int *pos = nullptr;                 // Tjds*: TJDS position of each stream entry
+    const int *pos = nullptr;                 // Tjds*: TJDS position of each stream entry                          (Csr16P: code8)
     const int *start_pos = nullptr;           // TjdsS
-    const int *ovf_ptr = nullptr;             // TjdsS: ntiles + 1 bounds of the tiles' overflow entries in ovf_val / ovf_k
-    const double *ovf_val = nullptr;          // TjdsS: value ...
+    const int *ovf_ptr = nullptr;             // TjdsS: ntiles + 1 bounds of the tiles' overflow entries in ovf_val / ovf_k   (Csr16P: esc_ptr)
+    const double *ovf_val = nullptr;          // TjdsS: value ...                                                    (Csr16P: esc_val)
     const int *ovf_k = nullptr;               // TjdsS: ... and permuted column of the entries [e, tile_next) of each tile, row order
     const int *cache_ptr = nullptr;           // TjdsS: ntiles + 1 bounds of the tiles' runs in val_cache (a tile's last entries)
-    const double *val_cache = nullptr;        // TjdsS: values of the entries whose val lines scatter over many tiles, tile by tile
+    const double *val_cache = nullptr;        // TjdsS: values of the entries whose val lines scatter over many tiles, tile by tile   (Csr16P: hot)
     const unsigned short *col16 = nullptr;    // Csr16: column - col_base[tile] per entry
     const int *col_base = nullptr;            // Csr16: smallest column of every tile
     const unsigned *word32 = nullptr;         // TjdsH, per entry: low 16 bits of its position (cached entries: of its permuted column) | (slot | run hint << kSlotBits) << 16
@@ -120,7 +130,21 @@ inline OwnerExtra owner_extra_of(const OwnerLaunch &l, unsigned long long *stamp
     ex.unit_x = l.unit_x, ex.word32 = l.word32, ex.group_run = l.group_run, ex.run_ptr = l.run_ptr, ex.run_tab = l.run_tab;
     ex.row_rel = l.row_rel;
     ex.stamps = stamps;
+    if (l.code8)  // Csr16P (never together with the TJDS arrays whose words these take)
+        ex.pos = reinterpret_cast<const int *>(l.code8), ex.ovf_ptr = l.esc_ptr, ex.ovf_val = l.esc_val, ex.val_cache = l.hot;
     return ex;
+}
+
+// Csr16P's arrays as the kernel reads them out of an OwnerExtra (see there)
+struct PackedArrays {
+    const unsigned char *__restrict__ code8;  // per entry of a packable tile, in col16_slot order: 0 ... 63 = index into hot, kEscapeCode = escape
+    const int *__restrict__ esc_ptr;          // 4 * ntiles + 1 starts of the wavefronts' runs in esc_val (a tile that is not packable: ~start, negative)
+    const double *__restrict__ esc_val;       // the escapes' values in the order (tile, wavefront, lane, k), every run padded to an even count
+    const double *__restrict__ hot;           // kHotValues doubles, the matrix's most frequent bit patterns
+};
+__device__ __forceinline__ PackedArrays packed_arrays_of(const OwnerExtra &ex)
+{
+    return {reinterpret_cast<const unsigned char *>(ex.pos), ex.ovf_ptr, ex.ovf_val, ex.val_cache};
 }
 
 // what the helpers below need of the kernel's arguments
@@ -139,7 +163,7 @@ struct OwnerArgs {
 template <int FLAVOR>
 __device__ __forceinline__ double owner_product_slow(const OwnerArgs &a, long long j)
 {
-    if constexpr (FLAVOR == kFlavorCsr || FLAVOR == kFlavorCsr16)
+    if constexpr (FLAVOR == kFlavorCsr || FLAVOR == kFlavorCsr16 || FLAVOR == kFlavorCsr16P)
         return a.val[j] * a.x[a.col_ind[j]];
     else if constexpr (FLAVOR == kFlavorTjdsK)
         return a.val[a.pos[j]] * a.x[a.col_ind[j]];
@@ -198,11 +222,16 @@ __device__ __forceinline__ void owner_body(
     const double *__restrict__ x, double *__restrict__ y, const int *__restrict__ tile_row,
     const int *__restrict__ tile_next, int rows, int nnz_arg, int ntiles, int tile_group_arg, const OwnerExtra &ex, const int block, const int lane_salt = 0)
 {
+    // (Csr16P: ex.pos, ex.ovf_ptr, ex.ovf_val and ex.val_cache are NOT TJDS data but the packed arrays -- see OwnerExtra.  a.pos and
+    // a.ovf_val below are then code8 and esc_val under other types; the helpers that take `a` read them for the TJDS flavours alone,
+    // each behind `if constexpr` on FLAVOR, never behind a runtime test.  A flavour that reads them otherwise must not share the words.)
     const OwnerArgs a = {col_ind, val, x, ex.pos, ex.start_pos, ex.ovf_val, ex.ovf_k, FLAVOR == kFlavorTjdsH ? ex.unit_x : 0};
     constexpr int TILE = kStreamBlock * VPT;
     constexpr int QCAP = (TILE + kStreamOver) / kLongRow + 1;
-    constexpr bool CSR = FLAVOR == kFlavorCsr || FLAVOR == kFlavorCsr16;
-    constexpr bool COL16 = FLAVOR == kFlavorCsr16;
+    constexpr bool PACKED = FLAVOR == kFlavorCsr16P;  // Csr16 whose packable tiles read codes and escapes instead of val
+    static_assert(!PACKED || VPT == 8, "the packed values are laid out for 2048-entry tiles");
+    constexpr bool CSR = FLAVOR == kFlavorCsr || FLAVOR == kFlavorCsr16 || PACKED;
+    constexpr bool COL16 = FLAVOR == kFlavorCsr16 || PACKED;
     constexpr bool HALF = FLAVOR == kFlavorTjdsH;
     constexpr bool TJDS = FLAVOR == kFlavorTjdsK || FLAVOR == kFlavorTjdsS || HALF;
     constexpr bool SORTED = FLAVOR == kFlavorTjdsS || HALF;  // entries in TJDS order inside the tile, lane-strided
@@ -263,6 +292,13 @@ __device__ __forceinline__ void owner_body(
     double v[VPT];
     const bool full_tile = s + TILE <= (long long)nnz;  // every lane's entries exist (always, except in the last tile)
     int grp[HALF ? VPT : 1];  // TjdsH: run (inside the tile) of the first entry of this entry's group of 32
+    // Csr16P: is this tile packable (block-uniform); this lane's 8 codes, its entry of the hot table, its pairs of the wavefront's
+    // run [esc_at, esc_end) of escapes
+    [[maybe_unused]] bool packed_tile = false;
+    [[maybe_unused]] unsigned code_lo = 0, code_hi = 0;
+    [[maybe_unused]] int esc_at = 0, esc_end = 0;
+    [[maybe_unused]] double hot = 0.0;
+    [[maybe_unused]] double2v ev[PACKED ? 4 : 1];
     // TjdsH: the tile's run table ({base, sub} per run), one run per lane, requested with the tile's own streams: an entry
     // then takes its run's words from its wavefront's copy by cross-lane reads instead of a second, dependent trip to memory
     // in front of the gathers (tiles with more than 64 runs read the rest from memory)
@@ -313,6 +349,35 @@ __device__ __forceinline__ void owner_body(
                 for (int k = 0; k < VPT; k += 2)
                     *reinterpret_cast<int2 *>(&c[k]) = *reinterpret_cast<const int2 *>(a.col_ind + s + lane_entry(k));
             };
+            if constexpr (PACKED) {
+                // Packed values: everything a packable tile reads instead of val goes out here, ahead of the tile's offsets (whose
+                // unpacking waits for them inside its branch: after these, the wait covers one flight of loads and not two), and
+                // none of it depends on a loaded code -- the lane's 8 codes (one 8-byte load, 512 contiguous bytes per wavefront),
+                // hot[lane] (the table is 512 bytes that every tile reads: an L2 hit) and the wavefront's run of escapes, read
+                // coalesced: its bounds are two scalars at a wave-uniform address, lane l takes the pairs at start + 2 l + 128 i.
+                // Runs start at even places and have even (padded) lengths, so a pair is 16-byte aligned and whole inside the run.
+                const PackedArrays pk = packed_arrays_of(ex);
+                const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+                esc_at = pk.esc_ptr[4 * b + wv];
+                const int esc_next = pk.esc_ptr[4 * b + wv + 1];
+                esc_end = esc_next < 0 ? ~esc_next : esc_next;  // (the next tile may be one that is not packable)
+                packed_tile = esc_at >= 0;  // the same for the four wavefronts of a tile
+                if (packed_tile) {
+                    const int2v *mine = reinterpret_cast<const int2v *>(pk.code8 + s + ((t >> 6) * (64 * VPT) + (t & 63) * VPT));
+                    const int2v cw = STREAMED ? __builtin_nontemporal_load(mine) : *mine;
+                    code_lo = (unsigned)cw.x, code_hi = (unsigned)cw.y;
+                    hot = pk.hot[t & 63];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int at = esc_at + 2 * (t & 63) + 128 * i;
+                        ev[i] = double2v{0.0, 0.0};
+                        if (at < esc_end) {
+                            const double2v *src = reinterpret_cast<const double2v *>(pk.esc_val + at);
+                            ev[i] = STREAMED ? __builtin_nontemporal_load(src) : *src;
+                        }
+                    }
+                }
+            }
             if constexpr (COL16) {
                 const int base = ex.col_base[b];
                 if (base >= 0) {
@@ -348,12 +413,14 @@ __device__ __forceinline__ void owner_body(
                     *reinterpret_cast<int2v *>(&pj[k]) = __builtin_nontemporal_load(reinterpret_cast<const int2v *>(a.pos + s + lane_entry(k)));
             }
             if constexpr (CSR) {
+                if (!PACKED || !packed_tile) {
 #pragma unroll
-                for (int k = 0; k < VPT; k += 2) {  // (each instruction covers 1 KiB of val exactly once)
-                    if constexpr (STREAMED)
-                        *reinterpret_cast<double2v *>(&v[k]) = __builtin_nontemporal_load(reinterpret_cast<const double2v *>(a.val + s + lane_entry(k)));
-                    else
-                        *reinterpret_cast<double2 *>(&v[k]) = *reinterpret_cast<const double2 *>(a.val + s + lane_entry(k));
+                    for (int k = 0; k < VPT; k += 2) {  // (each instruction covers 1 KiB of val exactly once)
+                        if constexpr (STREAMED)
+                            *reinterpret_cast<double2v *>(&v[k]) = __builtin_nontemporal_load(reinterpret_cast<const double2v *>(a.val + s + lane_entry(k)));
+                        else
+                            *reinterpret_cast<double2 *>(&v[k]) = *reinterpret_cast<const double2 *>(a.val + s + lane_entry(k));
+                    }
                 }
             }
         } else {  // VPT == 1: 256-entry tiles for matrices too small to fill the chip with 1024-entry ones
@@ -513,6 +580,49 @@ __device__ __forceinline__ void owner_body(
         for (int k = 0; k < VPT; ++k)
             xk[k] = a.x[c[k]];
         const double xo = over0 ? a.x[co] : 0.0;
+        if constexpr (PACKED) {
+            if (packed_tile) {
+                // The values of a packable tile, without a further trip to memory and without a byte of LDS of its own: the
+                // wavefront's escapes are staged in ITS OWN 512-entry part of prod[] -- where its products land afterwards and
+                // which no other wavefront touches before the barrier (a wavefront has at most 512 escapes) -- and a hot value
+                // comes from the lane that holds it.  LDS executes one wavefront's accesses in order; the wavefront barriers and
+                // fences keep the compiler from moving the reads above the writes or the product stores above the reads.
+                double *part = prod + (t >> 6) * (64 * VPT);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    *reinterpret_cast<double2v *>(&part[2 * (t & 63) + 128 * i]) = ev[i];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                // this lane's escapes follow those of the lanes below it: entry k's share of them is a count of the set bits below
+                // this lane in the wavefront's mask for entry k (no cross-lane data movement at all)
+                unsigned code[VPT];
+                int before = 0;
+#pragma unroll
+                for (int k = 0; k < VPT; ++k) {
+                    code[k] = ((k < 4 ? code_lo : code_hi) >> (8 * (k & 3))) & 0xffu;
+                    const unsigned long long mask = __ballot(code[k] == (unsigned)kEscapeCode);
+                    before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, (unsigned)before));
+                }
+                const int hot_lo = __double2loint(hot), hot_hi = __double2hiint(hot);
+                int mine = 0;  // escapes among this lane's entries 0 ... k - 1
+#pragma unroll
+                for (int k = 0; k < VPT; ++k) {
+                    const bool escaped = code[k] == (unsigned)kEscapeCode;
+                    const int from = (int)(code[k] & 63u) << 2;
+                    const double hot_k = __hiloint2double(__builtin_amdgcn_ds_bpermute(from, hot_hi), __builtin_amdgcn_ds_bpermute(from, hot_lo));
+                    // (every lane reads, an entry that did not escape from a place inside the part that it then ignores: all eight
+                    // reads and the sixteen cross-lane reads go out together and are waited for once -- behind a branch per entry
+                    // the compiler waited for each read by itself)
+                    const double esc_k = part[(before + mine) & (64 * VPT - 1)];
+                    v[k] = escaped ? esc_k : hot_k;
+                    mine += escaped ? 1 : 0;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+        }
 #pragma unroll
         for (int k = 0; k < VPT; ++k)
             p[k] = v[k] * xk[k];
@@ -679,6 +789,9 @@ __global__ __launch_bounds__(kStreamBlock) void csr_stream_owner(
 // CSR flavours: the 1024- and 2048-entry tiles also have the read-once twin, the 256-entry tile has not.
 #define SMVP_OWNER_CSR_WIDE_FORMS(X) X(4, kFlavorCsr) X(8, kFlavorCsr) X(4, kFlavorCsr16) X(8, kFlavorCsr16)
 #define SMVP_OWNER_CSR_FORMS(X) X(1, kFlavorCsr) SMVP_OWNER_CSR_WIDE_FORMS(X)
+// Csr16P: 2048-entry tiles only; plain and read-once single launches (and their stamped twins), no repeating form -- the timed
+// entry points run a packed plan as stamped single launches (owner_repeat_grid answers 0, the repeating launcher refuses it).
+#define SMVP_OWNER_CSR_PACKED_FORMS(X) X(8, kFlavorCsr16P)
 // TJDS flavours: the tile-ordered ones (TjdsS, TjdsH) also have a repeating form, the row-ordered one (TjdsK) has not.
 #define SMVP_OWNER_TJDS_TILE_FORMS(X) \
     X(1, kFlavorTjdsS) X(4, kFlavorTjdsS) X(8, kFlavorTjdsS) X(1, kFlavorTjdsH) X(4, kFlavorTjdsH) X(8, kFlavorTjdsH)

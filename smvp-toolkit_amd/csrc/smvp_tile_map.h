@@ -61,4 +61,9 @@ SMVP_HOST_DEVICE inline __attribute__((always_inline)) int col16_slot(int o, int
     return w * chunk + l * vpt + k;
 }
 
+// The packed values of the same tiles (kFlavorCsr16P): one code per entry, kept in col16_slot order too -- an index into the hot
+// table, one entry per lane of a wavefront, or the escape code.
+constexpr int kHotValues = 64;
+constexpr int kEscapeCode = 255;
+
 }  // namespace smvp
