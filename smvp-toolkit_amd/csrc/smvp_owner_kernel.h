@@ -68,6 +68,10 @@ namespace smvp {
 //                  (escapes) wavefront by wavefront in the order the lanes hold them.  Every value is the double val holds, bit for
 //                  bit, and every row is summed as kFlavorCsr16 sums it: y is bit-identical.  Wide tiles, the last partial tile,
 //                  overflow entries and the slow paths read val itself.  (SMVP_CSR_KERNEL_STREAM_PACKED)
+//                  What the plan says of a tile -- its rows, its column base, where its escapes lie, whether it is packable -- is
+//                  six words of four arrays, requested together and waited for once, and a packable tile's phase 1 is
+//                  straight-line: every stream load in one flight behind them, one wait, the gathers
+//                  (profiles/tile_record_measured.txt).
 //   kFlavorTjdsK   TJDS by rows: the stream lists, row by row, the TJDS positions p of the row's entries (`pos`) and
 //                  their permuted columns k (`col_ind`): value val[p] gathered from the jagged-diagonal array,
 //                  operand x_perm[k] (the one-kernel TJDS product, see ensure_row_gather in the engine)
@@ -213,6 +217,51 @@ __device__ __forceinline__ double owner_overflow_product(const OwnerArgs &a, int
 #define SMVP_TJDS_NEUTRALISE 0
 #endif
 
+// Csr16P: the 8 values of this lane's entries of a packable tile from its codes (code_lo, code_hi), its entry of the hot table and
+// its pairs ev[] of the wavefront's escapes, without a further trip to memory and without a byte of LDS of its own: the
+// wavefront's escapes are staged in ITS OWN 512-entry part of prod[] -- where its products land afterwards and which no other
+// wavefront touches before the barrier (a wavefront has at most 512 escapes) -- and a hot value comes from the lane that holds
+// it.  LDS executes one wavefront's accesses in order; the wavefront barriers and fences keep the compiler from moving the reads
+// above the writes or the caller's product stores above the reads.
+__device__ __forceinline__ void packed_decode(double *part, double2v ev0, double2v ev1, double2v ev2, double2v ev3, unsigned code_lo,
+                                              unsigned code_hi, double hot, int lane, double (&v)[8])
+{
+    *reinterpret_cast<double2v *>(&part[2 * lane]) = ev0;
+    *reinterpret_cast<double2v *>(&part[2 * lane + 128]) = ev1;
+    *reinterpret_cast<double2v *>(&part[2 * lane + 256]) = ev2;
+    *reinterpret_cast<double2v *>(&part[2 * lane + 384]) = ev3;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // this lane's escapes follow those of the lanes below it: entry k's share of them is a count of the set bits below
+    // this lane in the wavefront's mask for entry k (no cross-lane data movement at all)
+    unsigned code[8];
+    int before = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        code[k] = ((k < 4 ? code_lo : code_hi) >> (8 * (k & 3))) & 0xffu;
+        const unsigned long long mask = __ballot(code[k] == (unsigned)kEscapeCode);
+        before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, (unsigned)before));
+    }
+    const int hot_lo = __double2loint(hot), hot_hi = __double2hiint(hot);
+    int mine = 0;  // escapes among this lane's entries 0 ... k - 1
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const bool escaped = code[k] == (unsigned)kEscapeCode;
+        const int from = (int)(code[k] & 63u) << 2;
+        const double hot_k = __hiloint2double(__builtin_amdgcn_ds_bpermute(from, hot_hi), __builtin_amdgcn_ds_bpermute(from, hot_lo));
+        // (every lane reads, an entry that did not escape from a place inside the part that it then ignores: all eight
+        // reads and the sixteen cross-lane reads go out together and are waited for once -- behind a branch per entry
+        // the compiler waited for each read by itself)
+        const double esc_k = part[(before + mine) & (64 * 8 - 1)];
+        v[k] = escaped ? esc_k : hot_k;
+        mine += escaped ? 1 : 0;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // The body of the owner kernel for workgroup number `block` of the launch's grid (the plain kernel passes blockIdx.x; the
 // repeating kernel below walks the same grid several times).  Every thread of the workgroup leaves through the same exit.
 // STREAMED: the full tiles' val loads (CSR flavours, VPT 4 and 8) and Csr16's 16-byte offset loads carry the read-once hint.
@@ -252,7 +301,10 @@ __device__ __forceinline__ void owner_body(
     // free of launch and event overhead (the engine reduces the slots, see stamp_reduce)
     unsigned long long *stamp = nullptr;
     if constexpr (STAMPED) {
-        stamp = ex.stamps + 2 * ((size_t)block * (kStreamBlock / 64) + (t >> 6));
+        if constexpr (FLAVOR == kFlavorCsr16P)  // (the wavefront's number as a scalar: the pointer then costs this form no vector register pair)
+            stamp = ex.stamps + 2 * ((size_t)block * (kStreamBlock / 64) + __builtin_amdgcn_readfirstlane(t >> 6));
+        else
+            stamp = ex.stamps + 2 * ((size_t)block * (kStreamBlock / 64) + (t >> 6));
         if ((t & 63) == 0)
             stamp[0] = wall_clock64();
     }
@@ -275,7 +327,8 @@ __device__ __forceinline__ void owner_body(
     // ---- phase 1: stream + gather + multiply.  Straight-line code, ordered so that nothing waits on more
     // than one dependent round trip: the tile's own index / value loads go out first (they depend on nothing
     // but the block index), then the plan words, then row_ptr for phase 2 and the overflow entries, then ALL
-    // gathers (index -> operand is the one dependence that cannot be avoided).
+    // gathers (index -> operand is the one dependence that cannot be avoided).  (Csr16P holds itself to it in the emitted code:
+    // the plan words go out in one flight of scalar loads, and a packable tile's loads stand in one block of their own, `fast` below.)
     // Lane layout of the row-ordered flavours (Csr, Csr16, TjdsK; the K2' block above has the reasons and the counts): a
     // wavefront takes 64 * VPT consecutive entries of the tile in slabs of 128, and of every slab its lane l has the two
     // entries 2 l and 2 l + 1 -- one 16-byte val load, one 4-byte word of two 16-bit offsets (8 bytes of col_ind / pos), two
@@ -299,6 +352,88 @@ __device__ __forceinline__ void owner_body(
     [[maybe_unused]] int esc_at = 0, esc_end = 0;
     [[maybe_unused]] double hot = 0.0;
     [[maybe_unused]] double2v ev[PACKED ? 4 : 1];
+    // Csr16P: the tile's plan words -- its rows, the end of its last row, its column base, this wavefront's run of escapes (whose
+    // first word also says whether the tile is packable): six words of four arrays that depend on nothing but the tile number, so
+    // all four scalar loads go out together and are waited for ONCE.  `fast`: a full packable tile of a plan with row_rel takes the
+    // block below for its phase 1; every other tile the generic code, which finds these words loaded.
+    [[maybe_unused]] int pw_rlo = 0, pw_rhi = 0, pw_zend = 0, pw_base = 0;
+    bool fast = false;
+    [[maybe_unused]] double fast_p[PACKED ? VPT : 1], fast_po = 0.0;  // what the fast block hands to the common code: p[], po, rp_*
+    [[maybe_unused]] int fast_rp[4] = {0, 0, 0, 0};
+    if constexpr (PACKED) {
+        SMVP_PHASE(0);  // (diagnostic builds: this flavour's first phase starts at entry, the plan words' trip included)
+        const PackedArrays pk = packed_arrays_of(ex);
+        const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+        esc_at = pk.esc_ptr[4 * b + wv];
+        const int esc_next = pk.esc_ptr[4 * b + wv + 1];
+        pw_rlo = tile_row[b], pw_rhi = tile_row[b + 1];
+        pw_zend = tile_next[b];
+        pw_base = ex.col_base[b];
+        // (pinned: the compiler otherwise moves the loads whose words are used only behind the exit below past it -- a second trip)
+        asm volatile("" ::"s"(esc_next), "s"(pw_zend), "s"(pw_base));
+        if (pw_rlo == pw_rhi)
+            SMVP_OWNER_EXIT();  // all of this tile continues a row owned by an earlier tile
+        esc_end = esc_next < 0 ? ~esc_next : esc_next;  // (the next tile may be one that is not packable)
+        packed_tile = esc_at >= 0;  // the same for the four wavefronts of a tile
+        fast = full_tile && packed_tile && ex.row_rel != nullptr;
+        if (fast) {
+            // ---- phase 1 of a packable tile, straight-line: everything that depends on the plan words alone goes out in one flight
+            // -- hot[lane], the 8 codes, the masked escape pairs, the 8 offsets, this lane's row bounds for phase 2, the overflow
+            // entry -- then ONE wait, the offsets' unpacking, all gathers, the values' decode under them, the multiply.  No branch
+            // on a loaded word stands between two loads (a packable tile is narrow: no test of the base, no col_ind alternative).
+            const unsigned short *__restrict__ row_rel = ex.row_rel;
+            const int rlo = pw_rlo, rhi = pw_rhi, zend = pw_zend, base = pw_base;
+            const int lo = (int)s, ext = zend - (lo + TILE);
+            const bool over0 = ext <= kStreamOver && t < ext;  // (not the giant row's tile) this lane fetches overflow entry e + t
+            const int my = (t >> 6) * (64 * VPT) + (t & 63) * VPT;  // this lane's 8 entries in col16_slot order
+            hot = pk.hot[t & 63];
+            const int2v *codes = reinterpret_cast<const int2v *>(pk.code8 + s + my);
+            const int2v cw = STREAMED ? __builtin_nontemporal_load(codes) : *codes;
+            auto escapes = [&](int i) {  // pair i of this lane's, or zeros past the run's end
+                const int at = esc_at + 2 * (t & 63) + 128 * i;
+                double2v pair = {0.0, 0.0};
+                if (at < esc_end) {
+                    const double2v *src = reinterpret_cast<const double2v *>(pk.esc_val + at);
+                    pair = STREAMED ? __builtin_nontemporal_load(src) : *src;
+                }
+                return pair;
+            };
+            const double2v ev0 = escapes(0), ev1 = escapes(1), ev2 = escapes(2), ev3 = escapes(3);
+            const int4v *offs = reinterpret_cast<const int4v *>(ex.col16 + s + my);
+            const int4v w = STREAMED ? __builtin_nontemporal_load(offs) : *offs;
+            const int r1 = rlo + t, r2 = r1 + kStreamBlock;
+            if (r1 < rhi) {
+                fast_rp[0] = row_rel[r1];
+                fast_rp[1] = r1 + 1 < rhi ? (int)row_rel[r1 + 1] : zend - lo;
+            }
+            if (r2 < rhi) {
+                fast_rp[2] = row_rel[r2];
+                fast_rp[3] = r2 + 1 < rhi ? (int)row_rel[r2 + 1] : zend - lo;
+            }
+            int co = 0;
+            double vo = 0.0;
+            if (over0) {
+                co = a.col_ind[lo + TILE + t];
+                vo = a.val[lo + TILE + t];
+            }
+            code_lo = (unsigned)cw.x, code_hi = (unsigned)cw.y;
+            double xk[VPT];
+#pragma unroll
+            for (int k = 0; k < VPT; k += 2) {
+                xk[k] = a.x[base + (int)((unsigned)w[k / 2] & 0xffffu)];
+                xk[k + 1] = a.x[base + (int)((unsigned)w[k / 2] >> 16)];
+            }
+            double xo = over0 ? a.x[(unsigned)co] : 0.0;  // (unsigned: no sign extension, hence no wait, inside the overflow branch)
+            packed_decode(prod + (t >> 6) * (64 * VPT), ev0, ev1, ev2, ev3, code_lo, code_hi, hot, t & 63, v);
+            // (the overflow product needs nothing of the decode: pinned behind it, or the scheduler moves it -- and the wait for
+            // all gathers with it -- in front of the decode, which then no longer runs under the gathers)
+            asm volatile("" : "+v"(xo));
+#pragma unroll
+            for (int k = 0; k < VPT; ++k)
+                fast_p[k] = v[k] * xk[k];
+            fast_po = vo * xo;
+        }
+    }
     // TjdsH: the tile's run table ({base, sub} per run), one run per lane, requested with the tile's own streams: an entry
     // then takes its run's words from its wavefront's copy by cross-lane reads instead of a second, dependent trip to memory
     // in front of the gathers (tiles with more than 64 runs read the rest from memory)
@@ -342,7 +477,7 @@ __device__ __forceinline__ void owner_body(
                 }
             }
         }
-    } else if (full_tile) {
+    } else if (full_tile && !fast) {
         if constexpr (VPT >= 4) {
             auto load_cols = [&]() {
 #pragma unroll
@@ -354,14 +489,10 @@ __device__ __forceinline__ void owner_body(
                 // unpacking waits for them inside its branch: after these, the wait covers one flight of loads and not two), and
                 // none of it depends on a loaded code -- the lane's 8 codes (one 8-byte load, 512 contiguous bytes per wavefront),
                 // hot[lane] (the table is 512 bytes that every tile reads: an L2 hit) and the wavefront's run of escapes, read
-                // coalesced: its bounds are two scalars at a wave-uniform address, lane l takes the pairs at start + 2 l + 128 i.
+                // coalesced: its bounds are among the tile's plan words, lane l takes the pairs at start + 2 l + 128 i.
                 // Runs start at even places and have even (padded) lengths, so a pair is 16-byte aligned and whole inside the run.
+                // (This is the generic path: a packable tile comes here only in a plan without row_rel; esc_at and esc_end are set.)
                 const PackedArrays pk = packed_arrays_of(ex);
-                const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-                esc_at = pk.esc_ptr[4 * b + wv];
-                const int esc_next = pk.esc_ptr[4 * b + wv + 1];
-                esc_end = esc_next < 0 ? ~esc_next : esc_next;  // (the next tile may be one that is not packable)
-                packed_tile = esc_at >= 0;  // the same for the four wavefronts of a tile
                 if (packed_tile) {
                     const int2v *mine = reinterpret_cast<const int2v *>(pk.code8 + s + ((t >> 6) * (64 * VPT) + (t & 63) * VPT));
                     const int2v cw = STREAMED ? __builtin_nontemporal_load(mine) : *mine;
@@ -379,7 +510,11 @@ __device__ __forceinline__ void owner_body(
                 }
             }
             if constexpr (COL16) {
-                const int base = ex.col_base[b];
+                int base;
+                if constexpr (PACKED)
+                    base = pw_base;
+                else
+                    base = ex.col_base[b];
                 if (base >= 0) {
                     if constexpr (VPT == 8) {
                         // the plan keeps the offsets of a narrow 2048-entry tile in the order the lanes hold the entries
@@ -431,14 +566,23 @@ __device__ __forceinline__ void owner_body(
                 v[0] = a.val[j0];
         }
     }
-    const int rlo = tile_row[b];
-    const int rhi = tile_row[b + 1];
-    if (rlo == rhi)
-        SMVP_OWNER_EXIT();  // all of this tile continues a row owned by an earlier tile
-    SMVP_PHASE(0);
+    int rlo, rhi;
+    if constexpr (PACKED) {
+        rlo = pw_rlo, rhi = pw_rhi;  // (a tile in which no row starts left right after its plan words)
+    } else {
+        rlo = tile_row[b];
+        rhi = tile_row[b + 1];
+        if (rlo == rhi)
+            SMVP_OWNER_EXIT();  // all of this tile continues a row owned by an earlier tile
+        SMVP_PHASE(0);
+    }
     const int lo = (int)s;  // nnz < 2^31
     const int e = (int)(s + TILE < (long long)nnz ? s + TILE : (long long)nnz);
-    const int zend = tile_next[b];  // row_ptr[rhi]: end of the last owned row, >= e
+    int zend;  // row_ptr[rhi]: end of the last owned row, >= e
+    if constexpr (PACKED)
+        zend = pw_zend;
+    else
+        zend = tile_next[b];
     const int ext = zend - e;
     // bounds of owned row r as offsets from the tile's first entry: from the plan's 16-bit offsets where it keeps them (the
     // last owned row ends at zend), else from row_ptr
@@ -552,6 +696,13 @@ __device__ __forceinline__ void owner_body(
             if (over0)
                 po = unit_x ? a.val[co] : vo * a.x[co];
         }
+    } else if (fast) {  // Csr16P: phase 1 of this tile is done, above
+        if constexpr (PACKED) {
+#pragma unroll
+            for (int k = 0; k < VPT; ++k)
+                p[k] = fast_p[k];
+            po = fast_po, rp_a = fast_rp[0], rp_b = fast_rp[1], rp_a2 = fast_rp[2], rp_b2 = fast_rp[3];
+        }
     } else if (full_tile) {
         if (rlo + t < rhi)  // this lane's first row in phase 2
             row_bounds(rlo + t, rp_a, rp_b);
@@ -581,47 +732,8 @@ __device__ __forceinline__ void owner_body(
             xk[k] = a.x[c[k]];
         const double xo = over0 ? a.x[co] : 0.0;
         if constexpr (PACKED) {
-            if (packed_tile) {
-                // The values of a packable tile, without a further trip to memory and without a byte of LDS of its own: the
-                // wavefront's escapes are staged in ITS OWN 512-entry part of prod[] -- where its products land afterwards and
-                // which no other wavefront touches before the barrier (a wavefront has at most 512 escapes) -- and a hot value
-                // comes from the lane that holds it.  LDS executes one wavefront's accesses in order; the wavefront barriers and
-                // fences keep the compiler from moving the reads above the writes or the product stores above the reads.
-                double *part = prod + (t >> 6) * (64 * VPT);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    *reinterpret_cast<double2v *>(&part[2 * (t & 63) + 128 * i]) = ev[i];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                // this lane's escapes follow those of the lanes below it: entry k's share of them is a count of the set bits below
-                // this lane in the wavefront's mask for entry k (no cross-lane data movement at all)
-                unsigned code[VPT];
-                int before = 0;
-#pragma unroll
-                for (int k = 0; k < VPT; ++k) {
-                    code[k] = ((k < 4 ? code_lo : code_hi) >> (8 * (k & 3))) & 0xffu;
-                    const unsigned long long mask = __ballot(code[k] == (unsigned)kEscapeCode);
-                    before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, (unsigned)before));
-                }
-                const int hot_lo = __double2loint(hot), hot_hi = __double2hiint(hot);
-                int mine = 0;  // escapes among this lane's entries 0 ... k - 1
-#pragma unroll
-                for (int k = 0; k < VPT; ++k) {
-                    const bool escaped = code[k] == (unsigned)kEscapeCode;
-                    const int from = (int)(code[k] & 63u) << 2;
-                    const double hot_k = __hiloint2double(__builtin_amdgcn_ds_bpermute(from, hot_hi), __builtin_amdgcn_ds_bpermute(from, hot_lo));
-                    // (every lane reads, an entry that did not escape from a place inside the part that it then ignores: all eight
-                    // reads and the sixteen cross-lane reads go out together and are waited for once -- behind a branch per entry
-                    // the compiler waited for each read by itself)
-                    const double esc_k = part[(before + mine) & (64 * VPT - 1)];
-                    v[k] = escaped ? esc_k : hot_k;
-                    mine += escaped ? 1 : 0;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
+            if (packed_tile)  // (the values of a packable tile: from the codes, under the gathers)
+                packed_decode(prod + (t >> 6) * (64 * VPT), ev[0], ev[1], ev[2], ev[3], code_lo, code_hi, hot, t & 63, v);
         }
 #pragma unroll
         for (int k = 0; k < VPT; ++k)
