@@ -75,6 +75,7 @@ const char *smvp_version_string(void); /* "0.6.4" */
  *   "trsv_chain_width" 256 | 512 | 1024: the widest level a triangular solve's chain takes (default 256), read by smvp_csr_trsv_create and
  *                      smvp_csr_ilu0_create
  *   "trsv_lanes_by_mean" 1: a wide level's lanes per row from the triangle's mean row length alone (default: mean and longest row)
+ *   "color_max_blocks" n >= 1: the workgroups of one round of smvp_csr_color at the most (default 2048); the colours are the same
  * Unknown names are SMVP_ERR_INVALID. */
 int smvp_set_option(const char *name, int value);
 int smvp_get_option(const char *name, int *value); /* -1 = not set */
@@ -1421,6 +1422,83 @@ int smvp_csr_lsqr(smvp_csr_t *h, smvp_csr_t *ht, const smvp_lsqr_opts_t *opts, c
                   smvp_lsqr_result_t *result, double *rnorm_each, double *arnorm_each, void *stream);
 int smvp_tjds_lsqr(smvp_tjds_t *h, const smvp_lsqr_opts_t *opts, const double *d_b, const double *d_x0, double *d_x,
                    smvp_lsqr_result_t *result, double *rnorm_each, double *arnorm_each, void *stream);
+
+/* ------------------------------------------------------------ multicolour reordering */
+/* Colour the rows on the device, number them colour by colour, build B = P A P^T, kernel K23 (new: the reference only multiplies).
+ * A triangular solve (K15) and an ILU(0) (K17) cost one launch per level of their dependency graph, and natural orderings are deep
+ * (lap2d(1024): 2047 levels).  In B a row of colour c reads only rows of colours < c (LOWER) or > c (UPPER), so every plan made on
+ * B has at most `colors` levels.  B is an ordinary plain-CSR handle: K15 to K21 take it as it is.
+ *
+ * The colouring has ONE right answer.  Vertices are the rows 0 .. n-1 of the square handle h.  N(v) = the columns u != v stored in
+ * row v of h and, where ht is given (normally smvp_csr_create_transposed(h): the rows that store v), in row v of ht; repeats and
+ * explicit zeros count once, the diagonal does not count.  With a structurally symmetric h, or with ht, N is symmetric and the
+ * colouring is proper: no stored (i, j), i != j, joins two rows of one colour.  With an unsymmetric h and no ht the result is still
+ * the defined one, merely not proper: that can cost levels later, never a wrong number (the plans analyse B themselves).
+ *     key(v)   = mix32((uint32)v ^ seed)
+ *     mix32(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16      (32-bit wrap-around; a bijection)
+ *     color(v) = the smallest integer >= 0 that is not color(u) for any u in N(v) with key(u) > key(v)
+ *     depth(v) = 0 if no u in N(v) has a larger key, else 1 + the largest depth(u) over those u
+ * colors = 1 + max color(v) <= 1 + max |N(v)|, every colour below it is used; depth = 1 + max depth(v).  This is serial greedy
+ * colouring in descending key order, and what a Jones-Plassmann round scheme computes whatever its timing.
+ *
+ * smvp_csr_color runs rounds, one launch each.  d_color starts at -1 everywhere (written by the call).  A group of lanes_per_row
+ * lanes (2 .. 64, K15's rule on the rows' mean and longest length) takes a vertex without a colour and walks its row(s); a
+ * neighbour of larger key that has no colour yet leaves the vertex for the next launch -- no lane ever waits on a value another
+ * workgroup writes -- otherwise the group takes the first colour no such neighbour holds, in windows of 64 colours.  The host
+ * reads a counter after every round and stops when all n are coloured: 1 <= rounds <= depth for n > 0, and only `rounds` depends
+ * on timing.  The call therefore synchronises `stream`, allocates nothing but the counter, and leaves both handles' state alone
+ * (their products give the bits they gave before).
+ *   - SMVP_ERR_INVALID: a NULL h; a NULL d_color with n > 0; rows != cols; an ht of other dimensions or on another device; a
+ *     struct_size (opts or info) that is not this library's; max_rounds < 1; a capturing stream (nothing is enqueued, the capture
+ *     stays valid).  SMVP_ERR_UNSUPPORTED: a handle (h or ht) that is not plain CSR or is a row block; a run not finished after
+ *     max_rounds launches -- d_color is then unspecified, nothing is leaked.  SMVP_ERR_ALLOC as elsewhere.  Outputs are untouched
+ *     after every other failure.  n = 0 succeeds with colors 0 and rounds 0.
+ *   - info (may be NULL; set struct_size first): entries = the stored entries one full round reads (h's and ht's); build_ms = the
+ *     rounds' host wall time.  largest_class / smallest_class are counted on the host from one copy of d_color.
+ * smvp_csr_color_host is the definition on one core, no device touched: color (rows ints), *colors and *depth.  t_row_ptr /
+ * t_col_ind are both NULL or both set.  SMVP_ERR_INVALID for rows < 0, a NULL output, a NULL array that is needed, one of the two
+ * t_ arrays alone, a row_ptr that does not start at 0 or decreases, a column outside [0, rows); nothing is written then. */
+typedef struct smvp_color_opts {
+    unsigned struct_size; /* sizeof(smvp_color_opts_t), set by smvp_color_opts_default */
+    unsigned seed;        /* default 0 */
+    int max_rounds;       /* default 4096 */
+} smvp_color_opts_t;
+void smvp_color_opts_default(smvp_color_opts_t *o);
+typedef struct smvp_color_info {
+    unsigned struct_size;
+    int colors, rounds, largest_class, smallest_class, lanes_per_row;
+    long long entries;
+    double build_ms;
+} smvp_color_info_t;
+int smvp_csr_color(const smvp_csr_t *h, const smvp_csr_t *ht, const smvp_color_opts_t *opts, int *d_color, smvp_color_info_t *info,
+                   void *stream);
+int smvp_csr_color_host(int rows, const int *row_ptr, const int *col_ind, const int *t_row_ptr, const int *t_col_ind, unsigned seed,
+                        int *color, int *colors, int *depth);
+/* Classes (colours, or any labels in [0, classes)) to a permutation: the new order is by (class, old index) ascending, so it is
+ * stable.  d_old_of_new[p] = the element that lands at p, d_new_of_old[d_old_of_new[p]] = p (n ints each, on `device`);
+ * class_ptr (HOST, classes + 1 ints, may be NULL) delimits the classes in the new order.  Built on the library's stable radix sort
+ * and prefix sums; one workspace is allocated and freed, and the call returns after the work on `stream` has finished.  An element
+ * of d_class outside [0, classes) is SMVP_ERR_INVALID, found by a check kernel before anything indexes with it: nothing is written.
+ * SMVP_ERR_INVALID also for n < 0, classes < 0, a NULL device array with n > 0, a capturing stream. */
+int smvp_perm_from_classes(int device, int n, int classes, const int *d_class, int *d_old_of_new, int *d_new_of_old, int *class_ptr,
+                           void *stream);
+/* B = P A P^T as a handle: B(new_of_old[r], new_of_old[c]) = A(r, c) for ANY permutation the caller brings (a colouring is one
+ * source; an RCM or a nested dissection from elsewhere another).  *out is bit for bit smvp_csr_from_coo of the entries
+ * (new_of_old[r], new_of_old[c], val) listed in h's storage order: rows have ascending columns, ties in storage order, so a matrix
+ * without repeats that stores its diagonal qualifies for ILU(0).  It is smvp_csr_create_transposed's route and contract: one kernel
+ * writes the mapped COO list, smvp_csr_from_coo_device sorts it, the arrays are adopted; the result is an independent handle on
+ * AUTO that outlives h; a capturing stream is refused; SMVP_ERR_ALLOC leaks nothing; *out is NULL after every failure; the result
+ * is stale after h's val changes in place.  d_new_of_old (n ints on h's device) is validated on the device before any kernel
+ * indexes with it: a repeated or out-of-range element is SMVP_ERR_INVALID with nothing built.  Square plain-CSR handles only
+ * (rows != cols: SMVP_ERR_INVALID; a TJDS flavour or a row block: SMVP_ERR_UNSUPPORTED).
+ * B is a matrix in its own right: its product adds a row in ascending NEW column order, so (B P x) is P (A x) in exact
+ * arithmetic only -- the bits are B's, defined by B's arrays, not A's. */
+int smvp_csr_create_permuted(smvp_csr_t **out, const smvp_csr_t *h, const int *d_new_of_old, void *stream);
+/* d_out[p] = d_in[d_index[p]], p < n: with old_of_new this is P x, with new_of_old on the result x again, every bit of every
+ * element (signed zeros, NaN payloads).  Asynchronous on `stream`, allocates nothing, capturable.  An index outside [0, n) is not
+ * followed: that element of d_out gets a quiet NaN.  d_out must not overlap d_in (SMVP_ERR_INVALID, as a NULL array with n > 0
+ * and n < 0). */
+int smvp_vector_gather(int device, int n, const int *d_index, const double *d_in, double *d_out, void *stream);
 
 /* ------------------------------------------- several GPUs, one host process */
 /* New design (the reference is one CPU thread): the matrix is cut into `ngpus` row blocks balanced by entries

@@ -347,6 +347,47 @@ static int run_synth(const std::string &tmp)
                 ++g_bad;
         }
     }
+    // ---- K23's host side (smvp_reorder_host.cpp): the defaults, the checks of the two structs, and the colouring of the chain (two
+    // colours on a path whatever the seed), of the unsorted pattern with repeats and an empty row, alone and with itself as the
+    // second pattern, of a matrix without rows, and of arrays it must refuse
+    {
+        smvp_color_opts_t o;
+        smvp_color_opts_default(&o);
+        smvp_color_opts_default(nullptr);
+        smvp_color_info_t ci23{};
+        ci23.struct_size = sizeof ci23;
+        int bad23 = o.struct_size != sizeof o || o.seed != 0 || o.max_rounds != 4096 || smvp::color_check_opts("smvp_csr_color", &o, &ci23) != SMVP_OK ||
+                    smvp::color_check_opts("smvp_csr_color", nullptr, nullptr) != SMVP_OK;
+        o.max_rounds = 0;
+        bad23 += smvp::color_check_opts("smvp_csr_color", &o, nullptr) != SMVP_ERR_INVALID;
+        o.max_rounds = 1, o.struct_size = 8;
+        bad23 += smvp::color_check_opts("smvp_csr_color", &o, nullptr) != SMVP_ERR_INVALID;
+        ci23.struct_size = 4;
+        bad23 += smvp::color_check_opts("smvp_csr_color", nullptr, &ci23) != SMVP_ERR_INVALID;
+        int colors = -1, depth = -1;
+        mix_rp[2] = 5;  // (as it was before the refused analyses above)
+        for (unsigned seed : {0u, 1u, 0xffffffffu}) {
+            MUST(smvp_csr_color_host(n, chain_rp.data(), chain_c.data(), nullptr, nullptr, seed, chain_lv.data(), &colors, &depth));
+            // (i, i - 1) stored in one direction only: without the second pattern a vertex sees its predecessor alone
+            bad23 += colors != 2 || depth < 2;
+            MUST(smvp_csr_color_host(4, mix_rp.data(), mix_c.data(), nullptr, nullptr, seed, lv.data(), &colors, &depth));
+            bad23 += colors < 1 || colors > 3 || lv[3] != 0;
+            MUST(smvp_csr_color_host(4, mix_rp.data(), mix_c.data(), mix_rp.data(), mix_c.data(), seed, lv.data(), &colors, &depth));
+            bad23 += colors < 1 || colors > 3;
+        }
+        MUST(smvp_csr_color_host(0, nullptr, nullptr, nullptr, nullptr, 7, nullptr, &colors, &depth));
+        bad23 += colors != 0 || depth != 0;
+        int refused = smvp_csr_color_host(-1, mix_rp.data(), mix_c.data(), nullptr, nullptr, 0, lv.data(), &colors, &depth) == SMVP_ERR_INVALID;
+        refused += smvp_csr_color_host(4, mix_rp.data(), mix_c.data(), mix_rp.data(), nullptr, 0, lv.data(), &colors, &depth) == SMVP_ERR_INVALID;
+        refused += smvp_csr_color_host(4, mix_rp.data(), mix_c.data(), nullptr, nullptr, 0, nullptr, &colors, &depth) == SMVP_ERR_INVALID;
+        refused += smvp_csr_color_host(4, mix_rp.data(), mix_c.data(), nullptr, nullptr, 0, lv.data(), nullptr, &depth) == SMVP_ERR_INVALID;
+        mix_c[4] = 4;
+        refused += smvp_csr_color_host(4, mix_rp.data(), mix_c.data(), nullptr, nullptr, 0, lv.data(), &colors, &depth) == SMVP_ERR_INVALID;
+        mix_c[4] = 0;
+        printf("K23's host side: %d unexpected results, %d of 5 bad argument lists refused\n", bad23, refused);
+        if (bad23 || refused != 5)
+            ++g_bad;
+    }
     printf("version %s\n", smvp_version_string());
     return 0;
 }

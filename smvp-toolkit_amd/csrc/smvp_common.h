@@ -42,6 +42,24 @@ int ilu0_check(const char *fn, int rows, const int *row_ptr, const int *col_ind,
 // result or d_b, a struct_size that is not this library's, options out of range
 int lsqr_check_args(const char *fn, const void *h, const void *ht, bool needs_ht, const smvp_lsqr_opts_t *opts, const void *result,
                     const double *d_b);
+
+// K23, the multicolour ordering (smvp_reorder_host.cpp, smvp_reorder.hip): the key of vertex v is mix32(v ^ seed), a bijection on
+// 32-bit words; and what smvp_csr_color refuses of its two structs before any HIP call (either may be NULL)
+#ifdef __HIP__
+#define SMVP_HOST_DEVICE __host__ __device__
+#else
+#define SMVP_HOST_DEVICE
+#endif
+SMVP_HOST_DEVICE inline unsigned mix32(unsigned x)
+{
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+int color_check_opts(const char *fn, const smvp_color_opts_t *opts, const smvp_color_info_t *info);
 }  // namespace smvp
 
 // internal, device side (smvp_convert_device.hip): see its definition

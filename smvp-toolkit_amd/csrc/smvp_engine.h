@@ -163,6 +163,9 @@ struct CsrView {
     const int *h_row_ptr;
 };
 CsrView csr_view(const smvp_csr_t *h);
+// K23 (smvp_reorder.hip): a plain-CSR handle on AUTO over three device arrays this library allocated itself -- the handle frees
+// them when it is destroyed.  After a failure *out is NULL and the arrays are still the caller's to free.
+int csr_create_owning(smvp_csr_t **out, int device, int rows, int cols, int nnz, int *d_row_ptr, int *d_col_ind, double *d_val);
 
 // ---------------------------------------------------------------------------------------------------- the timed run
 // Per format: the {first, last} tick pairs one stamped product writes (0: the current plan cannot time itself on the device -- see

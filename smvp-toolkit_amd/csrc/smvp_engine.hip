@@ -874,6 +874,17 @@ int smvp::csr_create_tjds(smvp_csr_t **out, int device, int rows, int cols, int 
     return csr_create_impl(out, device, rows, cols, nnz, d_row_ptr, d_col_ind, d_val, SMVP_MEM_DEVICE, nullptr, flavor, &src);
 }
 
+int smvp::csr_create_owning(smvp_csr_t **out, int device, int rows, int cols, int nnz, int *d_row_ptr, int *d_col_ind, double *d_val)
+{
+    *out = nullptr;
+    smvp_csr_t *h = nullptr;
+    if (int rc = csr_create_impl(&h, device, rows, cols, nnz, d_row_ptr, d_col_ind, d_val, SMVP_MEM_DEVICE, nullptr, smvp::kFlavorCsr))
+        return rc;
+    h->own_row_ptr = h->own_col_ind = h->own_val = true;
+    *out = h;
+    return SMVP_OK;
+}
+
 bool smvp::csr_value_cache(const smvp_csr_t *h, int *min_tiles, long long *cached_entries)
 {
     const bool on = h && tile_ordered(h->flavor);

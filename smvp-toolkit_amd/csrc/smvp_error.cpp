@@ -48,6 +48,7 @@ Option g_options[] = {
     {"sharded_threads", {-1}},  // 1: smvp_sharded_* uses its issuing threads with ONE GPU too (default 0: the caller's thread)
     {"trsv_chain_width", {-1}}, // rows of the widest level a triangular solve's chain takes: 256 (default), 512 or 1024 -- a lane of its workgroup takes 1, 2 or 4
     {"trsv_lanes_by_mean", {-1}}, // 1: a wide level's lanes per row from the triangle's mean row length alone (default 0: from the geometric mean of mean and longest)
+    {"color_max_blocks", {-1}}, // workgroups of one round of smvp_csr_color at the most, >= 1 (default 2048): a round's groups take further vertices in trips of the grid
     {"mm_threads", {-1}},       // threads of the Matrix Market tokeniser (default: up to 16 for files of 8 MB and more; 1 = serial; n > 1 forces the parallel path)
 };
 Option *find_option(const char *name)

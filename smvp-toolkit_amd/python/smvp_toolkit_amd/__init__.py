@@ -148,6 +148,15 @@ class Ilu0Info(C.Structure):
                 ("plan_bytes", C.c_double), ("build_ms", C.c_double)]
 
 
+class ColorOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("seed", C.c_uint), ("max_rounds", C.c_int)]
+
+
+class ColorInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint), ("colors", C.c_int), ("rounds", C.c_int), ("largest_class", C.c_int),
+                ("smallest_class", C.c_int), ("lanes_per_row", C.c_int), ("entries", C.c_longlong), ("build_ms", C.c_double)]
+
+
 POWER_CONVERGED, POWER_MAX_STEPS, POWER_ZERO, POWER_NONFINITE = 0, 1, 2, 3
 TRSV_LOWER, TRSV_UPPER = 0, 1
 TRSV_DIAG_STORED, TRSV_DIAG_UNIT = 0, 1
@@ -200,6 +209,8 @@ EXPORTS = [
     "smvp_lsqr_opts_default", "smvp_csr_lsqr", "smvp_tjds_lsqr",
     "smvp_csr_ilu0_create", "smvp_ilu0_factor", "smvp_ilu0_matrix", "smvp_ilu0_info", "smvp_ilu0_destroy", "smvp_csr_ilu0_check",
     "smvp_csr_ilu0_host",
+    "smvp_color_opts_default", "smvp_csr_color", "smvp_csr_color_host", "smvp_perm_from_classes", "smvp_csr_create_permuted",
+    "smvp_vector_gather",
     "smvp_tjds_create", "smvp_tjds_set_x", "smvp_tjds_zero_y", "smvp_tjds_spmv",
     "smvp_tjds_set_ref_quirks", "smvp_tjds_set_mode", "smvp_tjds_set_tile", "smvp_tjds_set_value_cache", "smvp_tjds_get_value_cache", "smvp_tjds_describe", "smvp_tjds_destroy",
     "smvp_shard_opts_default", "smvp_csr_sharded_create", "smvp_csr_sharded_create_ex", "smvp_tjds_sharded_create",
@@ -296,6 +307,13 @@ def lib():
         L.smvp_ilu0_destroy.restype = None
         L.smvp_csr_ilu0_check.argtypes = [ci, vp, vp, vp, C.POINTER(ci)]
         L.smvp_csr_ilu0_host.argtypes = [ci, vp, vp, vp, vp]
+        L.smvp_color_opts_default.argtypes = [C.POINTER(ColorOpts)]
+        L.smvp_color_opts_default.restype = None
+        L.smvp_csr_color.argtypes = [vp, vp, C.POINTER(ColorOpts), vp, C.POINTER(ColorInfo), vp]
+        L.smvp_csr_color_host.argtypes = [ci, vp, vp, vp, vp, C.c_uint, vp, C.POINTER(ci), C.POINTER(ci)]
+        L.smvp_perm_from_classes.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp]
+        L.smvp_csr_create_permuted.argtypes = [C.POINTER(vp), vp, vp, vp]
+        L.smvp_vector_gather.argtypes = [ci, ci, vp, vp, vp, vp]
         L.smvp_tjds_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp, vp, ci]
         L.smvp_tjds_set_x.argtypes = [vp, vp, vp]
         L.smvp_tjds_zero_y.argtypes = [vp, vp, vp]
@@ -966,6 +984,74 @@ def ilu0_host(rows, row_ptr, col_ind, val):
     return out[:nnz]
 
 
+def color_host(rows, row_ptr, col_ind, t_row_ptr=None, t_col_ind=None, seed=0):
+    """(color, colors, depth): the multicolour ordering's definition on one core (smvp_csr_color_host, K23), no device touched.
+    t_row_ptr / t_col_ind: the transposed pattern, both or neither."""
+    rp, ci = _arr(row_ptr, np.int32), _arr(col_ind, np.int32)
+    trp = None if t_row_ptr is None else _arr(t_row_ptr, np.int32)
+    tci = None if t_col_ind is None else _arr(t_col_ind, np.int32)
+    color = np.zeros(max(int(rows), 1), dtype=np.int32)
+    colors, depth = C.c_int(), C.c_int()
+    _check(lib().smvp_csr_color_host(int(rows), _p(rp), _p(ci), None if trp is None else _p(trp), None if tci is None else _p(tci),
+                                     int(seed) & 0xffffffff, _p(color), C.byref(colors), C.byref(depth)), "smvp_csr_color_host")
+    return color[:max(int(rows), 0)], colors.value, depth.value
+
+
+def _int32_vector(name, t, n):
+    _device_vectors(**{name: t})
+    if str(t.dtype) != "torch.int32" or t.numel() != n or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous int32 tensor of %d elements (it has %d of %s)" % (name, n, t.numel(), t.dtype))
+
+
+def perm_from_classes(classes_tensor, n_classes, stream=None):
+    """(old_of_new, new_of_old, class_ptr) of an int32 CUDA tensor of classes in [0, n_classes) (smvp_perm_from_classes, K23): the
+    new order is by (class, old index) ascending.  The first two are int32 CUDA tensors, class_ptr a numpy array of n_classes + 1."""
+    import torch
+
+    n = classes_tensor.numel()
+    _int32_vector("classes_tensor", classes_tensor, n)
+    old_of_new = torch.empty(n, dtype=torch.int32, device=classes_tensor.device)
+    new_of_old = torch.empty(n, dtype=torch.int32, device=classes_tensor.device)
+    class_ptr = np.zeros(max(int(n_classes), 0) + 1, dtype=np.int32)
+    _check(lib().smvp_perm_from_classes(classes_tensor.device.index or 0, n, int(n_classes), _dev_ptr(classes_tensor), _dev_ptr(old_of_new),
+                                        _dev_ptr(new_of_old), _p(class_ptr), _stream_ptr(stream)), "smvp_perm_from_classes")
+    return old_of_new, new_of_old, class_ptr
+
+
+def vector_gather(index, src, out, stream=None):
+    """out[p] = src[index[p]] (smvp_vector_gather, K23): index an int32, src and out float64 CUDA tensors of one length, out not
+    overlapping src.  Asynchronous on `stream`.  Returns out."""
+    _device_vectors(src=src, out=out)
+    n = index.numel()
+    _int32_vector("index", index, n)
+    for name, t in (("src", src), ("out", out)):
+        if str(t.dtype) != "torch.float64" or t.numel() != n or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 tensor of %d elements (it has %d of %s)" % (name, n, t.numel(), t.dtype))
+    _check(lib().smvp_vector_gather(index.device.index or 0, n, _dev_ptr(index), _dev_ptr(src), _dev_ptr(out), _stream_ptr(stream)),
+           "smvp_vector_gather")
+    return out
+
+
+class Multicolored:
+    """A CsrMatrix in multicolour order (CsrMatrix.multicolored, K23): `matrix` = P A P^T, a CsrMatrix of its own; old_of_new and
+    new_of_old, int32 CUDA tensors; color_ptr, where every colour's rows begin in the new order; colors; info, smvp_csr_color's."""
+
+    def __init__(self, matrix, old_of_new, new_of_old, color_ptr, info):
+        self.matrix, self.old_of_new, self.new_of_old, self.color_ptr, self.info = matrix, old_of_new, new_of_old, color_ptr, info
+        self.colors = info["colors"]
+
+    def to_new(self, v, out, stream=None):
+        """out = P v: a vector of A's numbering in B's."""
+        return vector_gather(self.old_of_new, v, out, stream)
+
+    def to_old(self, v, out, stream=None):
+        """out = P^T v: a vector of B's numbering in A's."""
+        return vector_gather(self.new_of_old, v, out, stream)
+
+    def close(self):
+        self.matrix.close()
+
+
 class Ilu0:
     """An ILU(0) of a CsrMatrix on its own pattern (smvp_ilu0_t, K17).  `matrix` is the factor as a CsrMatrix over a handle this
     object owns: strictly below the diagonal L (unit diagonal implied), on and above it U.  It borrows the CsrMatrix's device arrays
@@ -1196,6 +1282,38 @@ class CsrMatrix:
         h = C.c_void_p()
         _check(lib().smvp_csr_create_transposed(C.byref(h), self._h, _stream_ptr(stream)), "smvp_csr_create_transposed")
         return CsrMatrix._wrap(h, self.cols, self.rows, self.nnz)
+
+    def color(self, color_out, at=None, seed=0, max_rounds=4096, stream=None):
+        """The multicolour ordering's colours into color_out, an int32 CUDA tensor of `rows` elements (smvp_csr_color, K23); at: the
+        CsrMatrix of A^T for a matrix that is not structurally symmetric.  Returns smvp_color_info_t as a dict."""
+        _int32_vector("color_out", color_out, self.rows)
+        o = ColorOpts()
+        lib().smvp_color_opts_default(C.byref(o))
+        o.seed, o.max_rounds = int(seed) & 0xffffffff, int(max_rounds)
+        i = ColorInfo()
+        i.struct_size = C.sizeof(ColorInfo)
+        _check(lib().smvp_csr_color(self._h, None if at is None else at._h, C.byref(o), _dev_ptr(color_out), C.byref(i), _stream_ptr(stream)),
+               "smvp_csr_color")
+        return {name: getattr(i, name) for name, _ in ColorInfo._fields_[1:]}
+
+    def permuted(self, new_of_old, stream=None):
+        """B = P A P^T as a CsrMatrix of its own (smvp_csr_create_permuted, K23): B[new_of_old[r], new_of_old[c]] = A[r, c] for an
+        int32 CUDA tensor that is a permutation of 0 .. rows-1.  Returns after the work on `stream` has finished."""
+        _int32_vector("new_of_old", new_of_old, self.rows)
+        h = C.c_void_p()
+        _check(lib().smvp_csr_create_permuted(C.byref(h), self._h, _dev_ptr(new_of_old), _stream_ptr(stream)), "smvp_csr_create_permuted")
+        return CsrMatrix._wrap(h, self.rows, self.cols, self.nnz)
+
+    def multicolored(self, at=None, seed=0, max_rounds=4096, stream=None):
+        """color -> perm_from_classes -> permuted, as a Multicolored: every triangular plan and ILU(0) made on its `matrix` has at most
+        `colors` levels (with a structurally symmetric matrix, or with `at`).  The tensors are made on torch's current device, which
+        must be the matrix's."""
+        import torch
+
+        color = torch.empty(self.rows, dtype=torch.int32, device="cuda")
+        info = self.color(color, at, seed, max_rounds, stream)
+        old_of_new, new_of_old, color_ptr = perm_from_classes(color, info["colors"], stream)
+        return Multicolored(self.permuted(new_of_old, stream), old_of_new, new_of_old, color_ptr, info)
 
     def device_arrays(self):
         """(row_ptr, col_ind, val): the device addresses the handle multiplies from, as ints; valid until close()."""
